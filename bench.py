@@ -9,14 +9,16 @@ One "step" = one full pass of the query over the rank's shard (all batches, redu
 N > 1 also the cross-device merge of the per-shard group tables).  N ranks = N shards (weak
 scaling): `value` = rows of all shards / max-over-ranks step time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch-rows B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch-rows B] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no torchrun environment spawns the N ranks itself (one process per GPU).
 Outside the timed region the final group table is verified key by key (aresdb_amd/check.py), the
 reference's own HOST build is timed on a bounded sample (cpu_baseline) and compared key by key with
 the same independent group-by, and a few secondary legs are reported (never `value`): the same query
 with the in-ABI fusion stages switched off, at the reference's live-batch size, and through the
-explicit fused extension.
+explicit fused extension.  `--dump-outputs DIR` writes the group table the last timed step returned to
+DIR/<name>.npy (dump_outputs): the shard is generated from a fixed seed, so two builds run with the same
+arguments can be compared array by array.
 """
 import argparse
 import gc
@@ -31,6 +33,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -222,6 +225,41 @@ def measure_traffic(batch_rows, timeout=240):
                      f"{batch_rows} rows per batch; read side x2: gfx950 counts 64 B per 128-B request)")
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: every file of the directory together
+
+
+def dump_outputs(directory, fetched, measure_dtype=np.float64):
+    """--dump-outputs: what a caller of the timed path holds after its last step — NativeQuery.fetch() of that step's
+    group table, one row per group — as DIR/<name>.npy: dim<q>_value (float64: exact for the 4-byte dimension slots)
+    and dim<q>_valid (float32, 0 = null) for the q-th group-by dimension, and measure (float64: exact for float64 sums,
+    uint32 counts and the integer sums of these shards).  HashReduce returns its groups in no defined order, and on
+    the GPU the order differs from run to run (which insert claims a table slot first), so the rows are written in
+    ascending order of their dimensions (dimension 0 first, a null before every value).  A table that would not fit
+    DUMP_MAX_BYTES is then cut to a fixed, seeded sample of its rows — the same rows of every array, order kept.
+    Returns (rows written, rows of the table)."""
+    dims, valids, meas = fetched
+    arrays = {}
+    for q, (d, v) in enumerate(zip(dims, valids)):
+        arrays[f"dim{q}_value"] = np.frombuffer(d, np.uint32).astype(np.float64)
+        arrays[f"dim{q}_valid"] = np.frombuffer(v, np.uint8).astype(np.float32)
+    arrays["measure"] = np.frombuffer(meas, measure_dtype).astype(np.float64)
+    n = len(arrays["measure"])
+    assert all(len(a) == n for a in arrays.values()), {k: len(a) for k, a in arrays.items()}
+    keys = [arrays[f"dim{q}_{what}"] for q in range(len(dims)) for what in ("valid", "value")]
+    if keys:
+        order = np.lexsort(keys[::-1])  # (lexsort's LAST key is the primary one)
+        arrays = {k: a[order] for k, a in arrays.items()}
+    npy_header = 128
+    keep = (DUMP_MAX_BYTES - npy_header * len(arrays)) // sum(a.itemsize for a in arrays.values())
+    if n > keep:
+        rows = np.sort(np.random.default_rng(20240229).choice(n, keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return min(n, keep), n
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` outside torchrun: one process per GPU (RANK / LOCAL_RANK /
     WORLD_SIZE from torch.distributed.run), rendezvous on 127.0.0.1."""
@@ -302,6 +340,8 @@ def single_process(args, backend=None, tensor_device=None):
             sync()
             state["elapsed"][r] = time.perf_counter() - t0
             state["merged"][r] = last.result_size
+            if args.dump_outputs and r == 0:
+                dump_outputs(args.dump_outputs, last.fetch())
             if args.verify_merged and r == 0:
                 every = []
                 for q in range(n):
@@ -467,6 +507,9 @@ def main(argv=None, backend=None, tensor_device=None):
                     help="archive batches: rows sorted by (ts, d3), both run-length encoded (mode 3) — decoded once per batch inside the "
                          "ABI, everything else on the same fast path (secondary leg)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the group table of the LAST timed step (N > 1: the merged one) to "
+                         "DIR/<name>.npy — see dump_outputs")
     ap.add_argument("--single-process", action="store_true",
                     help="N shards on N GPUs as N threads of THIS process (the reference's process model, "
                          "query/device_manager.go:185-218), merged through the in-process communicator: not the contract "
@@ -549,6 +592,7 @@ def main(argv=None, backend=None, tensor_device=None):
     plan.use_fused_extension = bool(args.fused_extension)
     # columns the plan reads (dimensions + measure + the filter's d1 [+ ts of the time filters]): the algorithmic bytes per row
     measure_columns = {"": {"m"}, "count": set(), "sum": {"d2"}}[args.sort_path]
+    measure_dtype = {"": "<f8", "count": "<u4", "sum": "<i8"}[args.sort_path]  # how the fetched measure bytes read
     plan_columns = sorted(set(dims) | measure_columns | {"d1"} | ({"ts"} if ts_range else set()))
 
     # the independent group-by a result is compared with, and the comparison: HashReduce identifies groups by their 32-bit
@@ -560,7 +604,7 @@ def main(argv=None, backend=None, tensor_device=None):
         if not args.sort_path:
             return check.compare_result(fetched, expected, hash_identity=True, dims=dims, eight=args.eight_dims)
         return check.compare_result(fetched, expected, hash_identity=False, dims=dims, ordered=True, eight=args.eight_dims,
-                                    measure_dtype={"count": "<u4", "sum": "<i8"}[args.sort_path])
+                                    measure_dtype=measure_dtype)
 
     def sync():
         if on_gpu:
@@ -693,6 +737,8 @@ def main(argv=None, backend=None, tensor_device=None):
     sync()
     elapsed = time.perf_counter() - t0
     drv1 = be.mem_driver_calls(device_index)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last.fetch(), measure_dtype)
     # ---- per-kernel durations: the same steps once more with HIP events around every launch (on the launch's own
     # stream, inside the library) — outside the timed region, so that the events cost `value` nothing; the pass's
     # own wall time is reported next to ms_per_step

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 import harness as H
 
 
@@ -33,7 +35,8 @@ def test_two_rank_path_merges_and_verifies(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(H.ROOT, "tests", "bench_dist_harness.py"), "--gpus", "2", "--rows", "6000",
-           "--batch-rows", "2500", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-legs", "--verify-merged"]
+           "--batch-rows", "2500", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-legs", "--verify-merged",
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, cwd=H.ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
@@ -43,6 +46,7 @@ def test_two_rank_path_merges_and_verifies(tmp_path):
     assert out["check_merged_groups"]["status"] == "ok"
     assert out["config"]["merged_groups"] == out["check_merged_groups"]["groups"] >= out["config"]["groups_per_shard"]
     assert len(out["per_rank_ms_per_step"]) == 2
+    assert len(np.load(tmp_path / "dump" / "measure.npy")) == out["config"]["merged_groups"]  # rank 0 dumps the MERGED table
 
 
 def test_eight_rank_path_merges_and_verifies():
@@ -63,15 +67,16 @@ def test_eight_rank_path_merges_and_verifies():
     assert out["config"]["merged_groups"] == out["check_merged_groups"]["groups"] >= out["config"]["groups_per_shard"]
 
 
-def test_single_process_threads_path_merges_and_verifies(capsys):
+def test_single_process_threads_path_merges_and_verifies(capsys, tmp_path):
     """bench.py --single-process: shards as threads of one process (the reference's process model), here two threads
     on the oracle backend; the merged table is checked key by key."""
     import sys as _sys
     _sys.path.insert(0, H.ROOT)
     import bench
     rc = bench.main(["--gpus", "2", "--single-process", "--rows", "6000", "--batch-rows", "2500", "--steps", "1", "--warmup", "0",
-                     "--verify-merged"], backend=H.oracle_backend(), tensor_device="cpu")
+                     "--verify-merged", "--dump-outputs", str(tmp_path / "dump")], backend=H.oracle_backend(), tensor_device="cpu")
     out = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
     assert rc == 0 and out["n_gpus"] == 2 and out["check_merged_groups"]["status"] == "ok"
     assert out["config"]["merged_groups"] == out["check_merged_groups"]["groups"] > 1000
     assert "THREAD" in out["config"]["parallelism"]
+    assert len(np.load(tmp_path / "dump" / "measure.npy")) == out["config"]["merged_groups"]
