@@ -43,10 +43,11 @@ struct FastOperands {
   const uint32_t *idx;   // index vector or nullptr (identity)
   int pad;
   int divLike;           // integer Divide / Mod / Floor by the constant: multiply-high division
-  int debug;             // ARES_F_DEBUG: timing experiments only
+  int streaming;         // non-zero: the column is read once, its loads are non-temporal (set by run_filter_rows)
   int step;              // bytes per stored value: 4, or 2 / 1 (Int16 / Uint16 / Int8 / Uint8 / SmallEnum / BigEnum columns,
                          // widened in registers — sign-extended for akind K_I32 — as query/iterator.hpp:146-165 does)
 };
+static_assert(sizeof(FastOperands) == 80, "FastOperands is a kernel argument, and the generated kernels' host code reads its fields");
 // bytes of `rows` values of the operand's column
 __host__ __device__ inline uint64_t fast_value_bytes(const FastOperands &f, uint64_t rows) { return static_cast<uint64_t>(f.step ? f.step : 4) * rows; }
 
@@ -273,11 +274,6 @@ inline bool fast_operands(const EvalParams &p, FastOperands &f, bool compareOnly
   f.bok = p.b.cok;
   f.idx = p.needRow ? p.idx : nullptr;
   f.divLike = p.arity == 2 && (p.I == K_I32 || p.I == K_U32) && (p.functor == Divide || p.functor == Mod || p.functor == Floor);
-  static const int debug = [] {  // kernel-variant switch of the filter experiments (tools/)
-    const char *dbg = getenv("ARES_F_DEBUG");
-    return dbg ? atoi(dbg) : 0;
-  }();
-  f.debug = debug;
   f.step = p.a.step;
   return true;
 }

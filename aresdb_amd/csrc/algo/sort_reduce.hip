@@ -418,11 +418,10 @@ void sort_rows(const uint8_t *dimValues, const DimLayoutD &L, size_t capacity, c
                 kBlock, stream, keyVector, length);
     return;
   }
-  // keys per lane and tile of a pass: 16 (4096-key tiles, 54 KB of LDS: two workgroups per compute unit) or 8 (2048-key
-  // tiles, 27 KB: five) — ARES_SORT_KPT
-  static EnvSwitch<int> keysPerLane("ARES_SORT_KPT", [](const char *e) { return e && atoi(e) == 8 ? 8 : 16; });
-  const int kpt = keysPerLane.get();
-  const int sortTile = kBlock * kpt;
+  // keys per lane and tile of a pass: 16 (4096-key tiles, 54 KB of LDS: two workgroups per compute unit); 8 (2048-key
+  // tiles, 27 KB: five) measured slower
+  constexpr int kSortKPT = 16;
+  const int sortTile = kBlock * kSortKPT;
   const int numTiles = (length + sortTile - 1) / sortTile;
   const size_t histBytes = 8 * 256 * sizeof(uint32_t);
   const size_t statusBytes = static_cast<size_t>(numTiles) * 256 * sizeof(uint32_t);
@@ -455,19 +454,14 @@ void sort_rows(const uint8_t *dimValues, const DimLayoutD &L, size_t capacity, c
   ARES_LAUNCH("sort_hash_hist_kernel", sort_hash_hist_kernel, grid, kBlock, stream, dimValues, L, capacity, rowIndex,
               keyVector, length, hist, hllValues, iotaPayload ? payload : nullptr);
   ARES_LAUNCH("digit_start_kernel", digit_start_kernel, 8, 256, stream, hist);
-  const int passGrid = capped_grid(numTiles, kpt == 8 ? 256 * 6 : 256 * 3);
+  const int passGrid = capped_grid(numTiles, 256 * 3);
   auto run_passes = [&](int first) {  // an even number of passes: the data ends where it started (keyVector / payload)
     for (int pass = first; pass < 8; pass++) {
       hip_check(hipMemsetAsync(status, 0, statusBytes, stream), "hipMemsetAsync");
       const bool even = ((pass - first) & 1) == 0;
-      if (kpt == 8)
-        ARES_LAUNCH("radix_pass_kernel", radix_pass_kernel<8>, passGrid, kBlock, stream, even ? keyVector : altKeys, even ? payload : altVals,
-                    even ? altKeys : keyVector, even ? altVals : payload, length, 8 * pass, hist + 256 * pass, tickets + pass, tickets + 8,
-                    status, numTiles);
-      else
-        ARES_LAUNCH("radix_pass_kernel", radix_pass_kernel<16>, passGrid, kBlock, stream, even ? keyVector : altKeys, even ? payload : altVals,
-                    even ? altKeys : keyVector, even ? altVals : payload, length, 8 * pass, hist + 256 * pass, tickets + pass, tickets + 8,
-                    status, numTiles);
+      ARES_LAUNCH("radix_pass_kernel", radix_pass_kernel<kSortKPT>, passGrid, kBlock, stream, even ? keyVector : altKeys, even ? payload : altVals,
+                  even ? altKeys : keyVector, even ? altVals : payload, length, 8 * pass, hist + 256 * pass, tickets + pass, tickets + 8,
+                  status, numTiles);
     }
   };
   run_passes(topOnly ? 4 : 0);

@@ -53,7 +53,6 @@
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
-#include <unistd.h>
 
 #include <algorithm>
 #include <map>
@@ -539,60 +538,6 @@ bool compaction_touches(const PendingCompact &c, const ByteRange &r) {
   return ri.overlaps(r) || rp.overlaps(r);
 }
 
-// ARES_FILTER_CHECK=<log file> (race hunting, see FilterCheck below): the bare-column jobs of a queue that was just
-// launched are checked against a copy of their column taken right behind the kernel; a mismatch is looked at again a
-// millisecond later — did the kernel read something that is no longer there (a writer racing with it) or is the column
-// itself not what the host uploaded?  Synchronises the queue's stream only.
-void transform_self_check(hipStream_t stream, const PendingQueue &q) {
-  static const char *path = getenv("ARES_FILTER_CHECK");
-  if (!path || !path[0] || q.n <= 0 || q.n > (1 << 20)) return;
-  const size_t n = static_cast<size_t>(q.n);
-  std::vector<uint32_t> idx(q.idx ? n : 0), out(n), vals, vals2;
-  std::vector<uint8_t> outOk(n), nulls, nulls2;
-  if (hipStreamSynchronize(stream) != hipSuccess) return;
-  if (q.idx && hipMemcpyAsync(idx.data(), q.idx, 4 * n, hipMemcpyDeviceToHost, stream) != hipSuccess) return;
-  for (int j = 0; j < q.jobs.count; j++) {
-    const FastOperands &f = q.jobs.f[j];
-    const SinkD &sk = q.jobs.s[j];
-    if (f.arity != 1 || sk.type == SINK_MEASURE || sk.width != 4 || f.step != 4 || !sk.nulls || f.akind == K_F32 || f.I == K_F32) continue;
-    const size_t rows = q.colRows[j], nb = f.nulls ? (rows + f.bitOff + 7) / 8 : 0;
-    vals.resize(rows); vals2.resize(rows); nulls.resize(nb); nulls2.resize(nb);
-    (void)hipMemcpyAsync(vals.data(), f.vals, 4 * rows, hipMemcpyDeviceToHost, stream);
-    if (nb) (void)hipMemcpyAsync(nulls.data(), f.nulls, nb, hipMemcpyDeviceToHost, stream);
-    (void)hipMemcpyAsync(out.data(), sk.values, 4 * n, hipMemcpyDeviceToHost, stream);
-    (void)hipMemcpyAsync(outOk.data(), sk.nulls, n, hipMemcpyDeviceToHost, stream);
-    if (hipStreamSynchronize(stream) != hipSuccess) return;
-    long bad = 0, firstBad = -1;
-    for (size_t i = 0; i < n; i++) {
-      const uint32_t row = q.idx ? idx[i] : static_cast<uint32_t>(i);
-      if (row >= rows) continue;
-      const uint32_t ok = nb ? (nulls[(row + f.bitOff) >> 3] >> ((row + f.bitOff) & 7)) & 1u : 1u;
-      if (out[i] != vals[row] || (outOk[i] != 0) != (ok != 0)) {
-        if (firstBad < 0) firstBad = static_cast<long>(i);
-        bad++;
-      }
-    }
-    if (!bad) continue;
-    usleep(1000);
-    (void)hipMemcpyAsync(vals2.data(), f.vals, 4 * rows, hipMemcpyDeviceToHost, stream);
-    if (nb) (void)hipMemcpyAsync(nulls2.data(), f.nulls, nb, hipMemcpyDeviceToHost, stream);
-    (void)hipStreamSynchronize(stream);
-    long colChanged = 0;
-    for (size_t r = 0; r < rows; r++) colChanged += vals[r] != vals2[r];
-    for (size_t b = 0; b < nb; b++) colChanged += nulls[b] != nulls2[b];
-    static std::mutex logMutex;
-    std::lock_guard<std::mutex> lock(logMutex);
-    if (FILE *o = fopen(path, "a")) {
-      const uint32_t row = q.idx ? idx[firstBad] : static_cast<uint32_t>(firstBad);
-      fprintf(o, "TRANSFORMCHECK MISMATCH job %d/%d n %d colRows %zu idx %p vals %p nulls %p out %p stream %p: %ld positions differ, first %ld "
-                 "(row %u: out %u ok %u, column %u then %u); column bytes that changed within 1 ms: %ld\n",
-              j, q.jobs.count, q.n, rows, (const void *)q.idx, (const void *)f.vals, (const void *)f.nulls, (const void *)sk.values, (void *)stream, bad,
-              firstBad, row, out[firstBad], outOk[firstBad], vals[row], vals2[row], colChanged);
-      fclose(o);
-    }
-  }
-}
-
 // caller holds the device's DeferLock and has selected the device.  inOrder: the launch is part of the
 // stream's own call sequence (a later call on the same stream follows); otherwise a queue the host
 // has already waited for is synchronised after its late launch.
@@ -618,7 +563,6 @@ void launch_queue(hipStream_t stream, PendingQueue &q, bool inOrder = false) {
     const int device = current_device();
     for (const ByteRange &w : q.writes) mem_note_write(device, w.lo, static_cast<size_t>(w.hi - w.lo));
   }
-  transform_self_check(stream, q);
   q.jobs.count = 0;
   q.reads.clear();
   q.writes.clear();
@@ -1498,166 +1442,6 @@ static int run_transform(const InputVector *ins, int arity, const OutputVector &
   return n;
 }
 
-// ---- ARES_FILTER_CHECK=<log file>: diagnostics for the two-phase filter (race hunting) -----------------------
-// Around the real predicate kernel the inputs (index vector, column values, validity bitmap) are copied to pinned
-// host memory on the SAME stream before and after it, the kernel is run a second time into scratch outputs, and
-// once the call's own read-back has synchronised the stream everything is compared: the two runs with each other,
-// the two input snapshots with each other, and a host evaluation of the predicate with both.  Same-stream work
-// only: nothing here synchronises the device or another stream.
-namespace {
-struct FilterCheckBuffers {
-  static constexpr int kMaxRows = 1 << 20;
-  uint8_t *dPred2 = nullptr;
-  uint32_t *dCounts2 = nullptr;  // [tile counts ... ][partials ...]
-  uint32_t *hIdx[2] = {nullptr, nullptr}, *hVals[2] = {nullptr, nullptr};
-  uint8_t *hNulls[2] = {nullptr, nullptr}, *hPred[2] = {nullptr, nullptr};
-  uint32_t *hParts2 = nullptr;
-  bool ok = false;
-  FilterCheckBuffers() {
-    bool good = hipMalloc(reinterpret_cast<void **>(&dPred2), kMaxRows + 64) == hipSuccess &&
-                hipMalloc(reinterpret_cast<void **>(&dCounts2), 4 * (kMaxRows / 4096 + 2 + 4096 + 16)) == hipSuccess;
-    for (int k = 0; k < 2 && good; k++) {
-      good = good && hipHostMalloc(reinterpret_cast<void **>(&hIdx[k]), 4ull * kMaxRows + 64, hipHostMallocPortable) == hipSuccess;
-      good = good && hipHostMalloc(reinterpret_cast<void **>(&hVals[k]), 4ull * kMaxRows + 64, hipHostMallocPortable) == hipSuccess;
-      good = good && hipHostMalloc(reinterpret_cast<void **>(&hNulls[k]), kMaxRows / 8 + 64, hipHostMallocPortable) == hipSuccess;
-      good = good && hipHostMalloc(reinterpret_cast<void **>(&hPred[k]), kMaxRows + 64, hipHostMallocPortable) == hipSuccess;
-    }
-    good = good && hipHostMalloc(reinterpret_cast<void **>(&hParts2), 4 * 4096 + 64, hipHostMallocPortable) == hipSuccess;
-    ok = good;
-    if (!good) (void)hipGetLastError();
-  }
-};
-const char *filter_check_path() {
-  static const char *p = getenv("ARES_FILTER_CHECK");
-  return (p && p[0]) ? p : nullptr;
-}
-uint32_t host_compare_fast(const FastOperands &f, uint32_t bits, uint32_t ok) {
-  auto asf = [](uint32_t b) { float x; memcpy(&x, &b, 4); return x; };
-  const uint32_t x = host_cvt32(bits, f.akind, f.I), y = host_cvt32(f.bbits, f.bkind, f.I);
-  const int ft = f.functor;
-  bool c;
-  if (f.I == K_F32) {
-    const float a = asf(x), b = asf(y);
-    c = ft == Equal ? a == b : ft == NotEqual ? a != b : ft == LessThan ? a < b : ft == LessThanOrEqual ? a <= b : ft == GreaterThan ? a > b : a >= b;
-  } else if (f.I == K_I32) {
-    const int32_t a = static_cast<int32_t>(x), b = static_cast<int32_t>(y);
-    c = ft == Equal ? a == b : ft == NotEqual ? a != b : ft == LessThan ? a < b : ft == LessThanOrEqual ? a <= b : ft == GreaterThan ? a > b : a >= b;
-  } else {
-    c = ft == Equal ? x == y : ft == NotEqual ? x != y : ft == LessThan ? x < y : ft == LessThanOrEqual ? x <= y : ft == GreaterThan ? x > y : x >= y;
-  }
-  return (ok && f.bok && c) ? 1u : 0u;
-}
-struct FilterCheck {
-  FilterCheckBuffers *b = nullptr;
-  FastOperands f;
-  uint32_t colRows = 0;
-  int n = 0, tiles = 0, predGrid = 0;
-  size_t nullBytes = 0;
-  const uint8_t *pred = nullptr;
-  hipStream_t stream = nullptr;
-  bool active = false;
-  void snapshot(int k) {
-    if (f.idx) (void)hipMemcpyAsync(b->hIdx[k], f.idx, 4ull * n, hipMemcpyDeviceToHost, stream);
-    (void)hipMemcpyAsync(b->hVals[k], f.vals, 4ull * colRows, hipMemcpyDeviceToHost, stream);
-    if (f.nulls) (void)hipMemcpyAsync(b->hNulls[k], f.nulls, nullBytes, hipMemcpyDeviceToHost, stream);
-  }
-  void begin(const FastOperands &fo, uint32_t rows, int n_, int tiles_, int predGrid_, const uint8_t *pred_, hipStream_t s) {
-    if (!filter_check_path() || fo.step != 4 || n_ > FilterCheckBuffers::kMaxRows || rows > static_cast<uint32_t>(FilterCheckBuffers::kMaxRows)) return;
-    thread_local FilterCheckBuffers bufs;
-    if (!bufs.ok) return;
-    b = &bufs;
-    f = fo;
-    colRows = rows;
-    n = n_;
-    tiles = tiles_;
-    predGrid = predGrid_;
-    pred = pred_;
-    stream = s;
-    nullBytes = f.nulls ? (static_cast<size_t>(colRows) + f.bitOff + 7) / 8 : 0;
-    active = true;
-    snapshot(0);
-  }
-  // right behind the real kernel, before anything rewrites the index vector
-  void after_kernel() {
-    if (!active) return;
-    snapshot(1);
-    (void)hipMemcpyAsync(b->hPred[0], pred, static_cast<size_t>(n), hipMemcpyDeviceToHost, stream);
-    (void)hipMemsetAsync(b->dCounts2, 0, 4ull * (tiles + predGrid + 4), stream);
-    // pred2 keeps the alignment phase of pred: the kernel's quad grid depends on it
-    uint8_t *pred2 = b->dPred2 + (reinterpret_cast<uintptr_t>(pred) & 3) + ((4 - (reinterpret_cast<uintptr_t>(b->dPred2) & 3)) & 3);
-    hipLaunchKernelGGL(filter_pred_kernel, dim3(predGrid), dim3(kBlock), 0, stream, f, pred2, b->dCounts2, n, tiles, b->dCounts2 + tiles + 2);
-    (void)hipMemcpyAsync(b->hPred[1], pred2, static_cast<size_t>(n), hipMemcpyDeviceToHost, stream);
-    (void)hipMemcpyAsync(b->hParts2, b->dCounts2 + tiles + 2, 4ull * predGrid, hipMemcpyDeviceToHost, stream);
-  }
-  // the stream has been synchronised by the call's own read-back
-  void finish(uint32_t count1) {
-    if (!active) return;
-    (void)hipStreamSynchronize(stream);
-    uint32_t count2 = 0;
-    for (int k = 0; k < predGrid; k++) count2 += b->hParts2[k];
-    uint32_t countHost[2] = {0, 0}, countPred[2] = {0, 0};
-    int firstIdxDiff = -1, idxDiffs = 0, firstValDiff = -1, valDiffs = 0, firstNullDiff = -1, nullDiffs = 0, firstPredDiff = -1, predDiffs = 0;
-    int firstHostDiff[2] = {-1, -1}, hostDiffs[2] = {0, 0};
-    for (int i = 0; i < n; i++) {
-      countPred[0] += b->hPred[0][i] != 0;
-      countPred[1] += b->hPred[1][i] != 0;
-      if (b->hPred[0][i] != b->hPred[1][i]) { if (firstPredDiff < 0) firstPredDiff = i; predDiffs++; }
-      if (f.idx && b->hIdx[0][i] != b->hIdx[1][i]) { if (firstIdxDiff < 0) firstIdxDiff = i; idxDiffs++; }
-      for (int k = 0; k < 2; k++) {
-        const uint32_t row = f.idx ? b->hIdx[k][i] : static_cast<uint32_t>(i);
-        uint32_t e = 0;
-        if (row < colRows) {
-          const uint32_t ok = f.nulls ? (b->hNulls[k][(row + f.bitOff) >> 3] >> ((row + f.bitOff) & 7)) & 1u : 1u;
-          e = host_compare_fast(f, b->hVals[k][row], ok);
-        }
-        countHost[k] += e;
-        if ((e != 0) != (b->hPred[0][i] != 0)) { if (firstHostDiff[k] < 0) firstHostDiff[k] = i; hostDiffs[k]++; }
-      }
-    }
-    for (uint32_t r = 0; r < colRows; r++)
-      if (b->hVals[0][r] != b->hVals[1][r]) { if (firstValDiff < 0) firstValDiff = static_cast<int>(r); valDiffs++; }
-    for (size_t k = 0; k < nullBytes; k++)
-      if (b->hNulls[0][k] != b->hNulls[1][k]) { if (firstNullDiff < 0) firstNullDiff = static_cast<int>(k); nullDiffs++; }
-    const bool bad = count1 != count2 || count1 != countPred[0] || predDiffs || idxDiffs || valDiffs || nullDiffs || hostDiffs[0] || hostDiffs[1];
-    static std::mutex logMutex;
-    std::lock_guard<std::mutex> lock(logMutex);
-    FILE *out = fopen(filter_check_path(), "a");
-    if (!out) return;
-    static long calls = 0;
-    calls++;
-    if (bad) {
-      fprintf(out, "FILTERCHECK MISMATCH call %ld n %d colRows %u idx %p vals %p nulls %p bitOff %u pred %p stream %p functor %d I %d akind %d bbits %u: "
-                   "count1 %u count2 %u countPred %u/%u countHost %u/%u predDiffs %d (first %d) idxDiffs %d (first %d) valDiffs %d (first %d) "
-                   "nullDiffs %d (first byte %d) hostVsPred %d/%d (first %d/%d)\n",
-              calls, n, colRows, (const void *)f.idx, (const void *)f.vals, (const void *)f.nulls, f.bitOff, (const void *)pred, (void *)stream, f.functor, f.I,
-              f.akind, f.bbits, count1, count2, countPred[0], countPred[1], countHost[0], countHost[1], predDiffs, firstPredDiff, idxDiffs,
-              firstIdxDiff, valDiffs, firstValDiff, nullDiffs, firstNullDiff, hostDiffs[0], hostDiffs[1], firstHostDiff[0], firstHostDiff[1]);
-      int shown = 0;
-      for (int i = 0; i < n && shown < 16; i++) {
-        const bool d = b->hPred[0][i] != b->hPred[1][i] || (f.idx && b->hIdx[0][i] != b->hIdx[1][i]);
-        bool hd = false;
-        uint32_t rows[2], vals[2] = {0, 0}, oks[2] = {1, 1};
-        for (int k = 0; k < 2; k++) {
-          rows[k] = f.idx ? b->hIdx[k][i] : static_cast<uint32_t>(i);
-          if (rows[k] < colRows) {
-            vals[k] = b->hVals[k][rows[k]];
-            oks[k] = f.nulls ? (b->hNulls[k][(rows[k] + f.bitOff) >> 3] >> ((rows[k] + f.bitOff) & 7)) & 1u : 1u;
-            hd = hd || ((host_compare_fast(f, vals[k], oks[k]) != 0) != (b->hPred[0][i] != 0));
-          }
-        }
-        if (d || hd) {
-          fprintf(out, "  pos %d: pred %u/%u row %u/%u val %u/%u ok %u/%u\n", i, b->hPred[0][i], b->hPred[1][i], rows[0], rows[1], vals[0], vals[1], oks[0], oks[1]);
-          shown++;
-        }
-      }
-    } else if (calls % 2000 == 1) {
-      fprintf(out, "filtercheck ok: %ld calls so far\n", calls);
-    }
-    fclose(out);
-  }
-};
-}  // namespace
-
 // ---- filters counted in row space (filter_rows_kernel) -----------------------------------------------------------
 namespace {
 // workgroups of `kernel` the device holds at once (occupancy x compute units), per device and kernel, asked once
@@ -1724,9 +1508,7 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
                     bool virtualIdx, const std::shared_ptr<StreamBuffer> &keep = nullptr) {
   f.idx = nullptr;
   f.pad = 0;
-  // streaming (non-temporal) column loads: the column is read once by this kernel — 0.060 -> 0.054 ms per 64 Mi rows
-  // (ARES_F_DEBUG=1024 switches them off)
-  if (!(f.debug & 1024)) f.debug |= 128;
+  f.streaming = 1;  // the column is read once by this kernel: 0.060 -> 0.054 ms per 64 Mi rows (profiles/r4_experiments.md)
   constexpr int kGridCap = 2048;  // two partial counts per workgroup come back in one copy
   static_assert(2 * kGridCap <= kPinnedWords, "the partial counts are read back in one copy");
   std::shared_ptr<StreamBuffer> bits1, bits2;
@@ -1804,11 +1586,6 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
       const int perUnit = std::max(1, std::min(resident / cus - 1, 6));
       grid = capped_grid(tiles, std::min(kGridCap, cus * perUnit));
     }
-    if (f.debug & 16) grid = capped_grid(tiles, kGridCap);        // (experiments: 2048 workgroups whatever fits at once,
-    if (f.debug & 32) grid = capped_grid(tiles, 256 * 4);         //  four / eight per compute unit)
-    if (f.debug & 64) grid = capped_grid(tiles, 256 * 8);
-    if ((f.debug >> 12) & 15) grid = capped_grid(tiles, 256 * ((f.debug >> 12) & 15));  // (experiment: workgroups per compute unit)
-    grid = std::min(grid, kGridCap);  // whatever the experiment switches asked for: two partial counts per workgroup fit the pinned slot
     const size_t bitBytes = static_cast<size_t>(tiles) * kBlock * sizeof(uint16_t);  // 16 rows per lane and tile
     bits1 = std::make_shared<StreamBuffer>(bitBytes, stream);
     if (two) bits2 = std::make_shared<StreamBuffer>(bitBytes, stream);
@@ -1850,6 +1627,161 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
   }
   return static_cast<int>(count);
 }
+
+// Settles what is pending on the device before a filter runs and says how the filter may run.  A filter of the hot shape
+// consumes a not-yet-written iota index vector directly (*virtualIdx); everything else that is pending on the device is
+// launched first.  Returns true when the filter may be counted in row space (run_filter_rows).
+bool prepare_filter(int device, hipStream_t stream, const EvalParams &p, uint32_t *indexVector, uint8_t *pred, int n,
+                    int numForeignTables, const uint32_t *baseCounts, bool *virtualIdx) {
+  bool rowSpace = false;
+  *virtualIdx = false;
+  FastOperands probe;
+  if (!is_wide(p.a.kind) && indexVector != nullptr && numForeignTables == 0 && fast_operands(p, probe, true)) {
+    *virtualIdx = virtual_iota(device, indexVector, n, true);
+    // ... and, while every filter of the batch has been of that shape, is only counted — over the batch's rows, with
+    // the filters before it (run_filter_rows): the pending ones of this very vector stay pending through the flush
+    rowSpace = baseCounts == nullptr && row_space_eligible(device, stream, indexVector, n, p.a.length);
+  }
+  if (rowSpace) flush_deferred_impl(device, nullptr, nullptr, indexVector);
+  else flush_deferred(device);
+  // (the flush may have applied them after all: queued transforms that read the vector were launched)
+  rowSpace = rowSpace && row_space_eligible(device, stream, indexVector, n, p.a.length);
+  if (!rowSpace) mem_note_write(device, pred, static_cast<size_t>(n));  // (a counted filter writes no predicate bytes unless it is replayed)
+  materialize_index_vector(device, indexVector);
+  return rowSpace;
+}
+
+// The two-phase path of a hot-shape filter: predicate + tile counts, scan, chain-free compaction of the index vector and of
+// every RecordID vector.  Without foreign tables and with a valid journal only the count is produced here; the compaction
+// is left pending (PendingCompact).
+int run_filter_two_phase(int device, hipStream_t stream, FastOperands f, uint32_t *indexVector, uint8_t *pred, int n,
+                         RecordID **recordIDVectors, int numForeignTables, bool virtualIdx) {
+  f.pad = static_cast<int>(reinterpret_cast<uintptr_t>(pred) & 3);
+  const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
+  const int tiles = static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
+  const int passes = 1 + numForeignTables;
+  // layout: [total, error, tickets[passes], pad][tileCounts][tileOffsets + 1][loaded x passes][one partial count per workgroup]
+  const size_t head = 64;
+  constexpr int kPredGridCap = 256 * 16;
+  static_assert(kPredGridCap <= kPinnedWords, "the partial counts are read back in one copy");
+  const int predGrid = capped_grid(tiles, kPredGridCap);
+  const size_t words = static_cast<size_t>(tiles) * (2 + passes) + 1 + static_cast<size_t>(predGrid);
+  auto wsBuf = std::make_shared<StreamBuffer>(head + 4 * words, stream);
+  uint32_t *w = wsBuf->as<uint32_t>();
+  uint32_t *total = w, *error = w + 1;
+  unsigned int *tickets = w + 2;
+  uint32_t *tileCounts = w + 16, *tileOffsets = tileCounts + tiles, *loaded = tileOffsets + tiles + 1;
+  hip_check(hipMemsetAsync(w, 0, head + 4 * words, stream), "hipMemsetAsync");  // one fill: head, counts, flags
+  if (virtualIdx) f.idx = nullptr;  // rows = position
+  // lazy: the tile offsets are computed when the compaction runs; with foreign tables they are needed at once
+  const bool lazy = numForeignTables == 0 && journal_is_valid(device, indexVector);
+  uint32_t *partials = loaded + static_cast<size_t>(tiles) * passes;
+  ARES_LAUNCH("filter_pred_kernel", filter_pred_kernel, predGrid, kBlock, stream, f, pred, tileCounts, n, tiles,
+              lazy ? partials : nullptr);
+  if (lazy) {
+    // The count is known; the compaction waits until somebody needs the compacted vector — a
+    // HashReduce that re-derives the survivors from the journal never does.
+    uint32_t parts[kPredGridCap];
+    read_back_u32(partials, parts, predGrid, stream);
+    uint32_t count = 0;
+    for (int b = 0; b < predGrid; b++) count += parts[b];
+    PendingCompact c;
+    c.device = device;
+    c.stream = stream;
+    c.idx = indexVector;
+    c.pred = pred;
+    c.n = n;
+    c.pad = f.pad;
+    c.tiles = tiles;
+    c.virtualIdx = virtualIdx;
+    c.ws = wsBuf;
+    c.ticket = tickets;
+    c.error = error;
+    c.tileOffsets = tileOffsets;
+    c.loaded = loaded;
+    c.tileCounts = tileCounts;
+    c.total = total;
+    DeferLock lock(device);
+    t_state->compactions[indexVector] = c;
+    return static_cast<int>(count);
+  }
+  ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, stream, tileCounts, tileOffsets, tiles, total);
+  const int cgrid = capped_grid((tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
+  mem_note_write(device, indexVector, 4ull * static_cast<size_t>(n));
+  for (int t = 0; t < numForeignTables; t++) mem_note_write(device, recordIDVectors[t], 8ull * static_cast<size_t>(n));
+  for (int pass = 0; pass < passes; pass++) {
+    CompactWorkspace cw;
+    cw.ticket = tickets + pass;
+    cw.error = error;
+    cw.tileOffsets = tileOffsets;
+    cw.loaded = loaded + static_cast<size_t>(tiles) * pass;
+    if (pass == 0 && virtualIdx)
+      ARES_LAUNCH("filter_compact_kernel<iota>", (filter_compact_kernel<uint32_t, true>), cgrid, kBlock, stream, pred, indexVector,
+                  0u, f.pad, cw, n, tiles);
+    else if (pass == 0)
+      ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, stream, pred, indexVector, 0u,
+                  f.pad, cw, n, tiles);
+    else
+      ARES_LAUNCH("filter_compact_kernel<rid>", (filter_compact_kernel<uint64_t, false>), cgrid, kBlock, stream, pred,
+                  reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), 0u, f.pad, cw, n, tiles);
+  }
+  uint32_t result[2] = {0, 0};  // {survivors, error}
+  read_back_u32(total, result, 2, stream);
+  if (result[1]) throw AlgorithmError("ERROR: filter: compaction wait timed out");
+  return static_cast<int>(result[0]);
+}
+
+// The generic path — wide operands (arr: an array operand), expressions outside the hot shape and their foreign-table
+// passes: one look-back kernel per pass evaluates (wide operands: reads) the predicate and compacts in place.  The index
+// vector has been written by now: only a hot-shape filter consumes a lazy iota.
+int run_filter_generic(int device, hipStream_t stream, EvalParams p, const ArrayD *arr, uint32_t *indexVector, uint8_t *pred, int n,
+                       RecordID **recordIDVectors, int numForeignTables) {
+  if (is_wide(p.a.kind)) {
+    // wide operands: evaluate the predicate with the wide transform kernel, then compact by pred
+    SinkD s;
+    bind_pred_sink(pred, s);
+    p.needRow = indexVector != nullptr;
+    const int grid = capped_grid((static_cast<int64_t>(n) + kBlock - 1) / kBlock);
+    if (arr)
+      launch_array(*arr, s, n, stream);
+    else
+      ARES_LAUNCH("transform_wide_kernel", transform_wide_kernel, grid, kBlock, stream, p, s, n);
+  }
+  mem_note_write(device, indexVector, 4ull * static_cast<size_t>(n));
+  for (int t = 0; t < numForeignTables; t++) mem_note_write(device, recordIDVectors[t], 8ull * static_cast<size_t>(n));
+  const int numTiles = static_cast<int>((static_cast<int64_t>(n) + kFilterTile - 1) / kFilterTile);
+  const int passes = 1 + numForeignTables;
+  const size_t passBytes = 16 + sizeof(uint64_t) * static_cast<size_t>(numTiles);
+  StreamBuffer wsBuf(passBytes * passes, stream);
+  hip_check(hipMemsetAsync(wsBuf.get(), 0, passBytes * passes, stream), "hipMemsetAsync");
+  const int grid = capped_grid(numTiles);
+  uint32_t *totalDev = nullptr;
+  for (int pass = 0; pass < passes; pass++) {
+    uint8_t *base = wsBuf.as<uint8_t>() + passBytes * pass;
+    ScanWorkspace ws;
+    ws.ticket = reinterpret_cast<unsigned int *>(base);
+    ws.total = reinterpret_cast<uint32_t *>(base + 4);
+    ws.error = reinterpret_cast<uint32_t *>(wsBuf.as<uint8_t>() + 8);  // shared by all passes
+    ws.status = reinterpret_cast<uint64_t *>(base + 16);
+    if (pass == 0) {
+      totalDev = ws.total;
+      if (is_wide(p.a.kind)) {
+        ARES_LAUNCH("filter_kernel<2>", filter_kernel<2>, grid, kBlock, stream, p, pred, indexVector,
+                           static_cast<uint64_t *>(nullptr), ws, n, numTiles);
+      } else {
+        ARES_LAUNCH("filter_kernel<0>", filter_kernel<0>, grid, kBlock, stream, p, pred, indexVector,
+                    static_cast<uint64_t *>(nullptr), ws, n, numTiles);
+      }
+    } else {
+      ARES_LAUNCH("filter_kernel<1>", filter_kernel<1>, grid, kBlock, stream, p, pred, indexVector,
+                  reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), ws, n, numTiles);
+    }
+  }
+  uint32_t result[2] = {0, 0};  // {survivors, error}
+  read_back_u32(totalDev, result, 2, stream);
+  if (result[1]) throw AlgorithmError("ERROR: filter: inter-tile scan timed out");
+  return static_cast<int>(result[0]);
+}
 }  // namespace
 
 static int run_filter(const InputVector *ins, int arity, uint32_t *indexVector, uint8_t *pred, int n,
@@ -1874,42 +1806,11 @@ static int run_filter(const InputVector *ins, int arity, uint32_t *indexVector, 
     decoded = decode_run_length_operand(device, stream, p.a, indexVector, baseCounts, startCount);
   }
   p.needRow = 1;
-  static const bool onePass = [] {
-    const char *e = getenv("ARES_FILTER");
-    return e && strcmp(e, "onepass") == 0;
-  }();
-  // a filter of the hot shape consumes a not-yet-written iota index vector directly; everything
-  // else that is pending on the device is launched first
-  bool virtualIdx = false, rowSpace = false;
-  {
-    FastOperands probe;
-    if (!is_wide(p.a.kind) && indexVector != nullptr && numForeignTables == 0 && fast_operands(p, probe, true)) {
-      virtualIdx = virtual_iota(device, indexVector, n, true);
-      // ... and, while every filter of the batch has been of that shape, is only counted — over the batch's rows, with
-      // the filters before it (run_filter_rows): the pending ones of this very vector stay pending through the flush
-      rowSpace = !onePass && baseCounts == nullptr && row_space_eligible(device, stream, indexVector, n, p.a.length);
-    }
-  }
-  if (rowSpace) flush_deferred_impl(device, nullptr, nullptr, indexVector);
-  else flush_deferred(device);
-  // (the flush may have applied them after all: queued transforms that read the vector were launched)
-  rowSpace = rowSpace && row_space_eligible(device, stream, indexVector, n, p.a.length);
-  if (!rowSpace) mem_note_write(device, pred, static_cast<size_t>(n));  // (a counted filter writes no predicate bytes unless it is replayed)
-  materialize_index_vector(device, indexVector);
-  if (is_wide(p.a.kind)) {
-    // wide operands: evaluate the predicate with the wide transform kernel, then compact by pred
-    SinkD s;
-    bind_pred_sink(pred, s);
-    p.needRow = indexVector != nullptr;
-    const int grid = capped_grid((static_cast<int64_t>(n) + kBlock - 1) / kBlock);
-    if (isArray)
-      launch_array(arr, s, n, stream);
-    else
-      ARES_LAUNCH("transform_wide_kernel", transform_wide_kernel, grid, kBlock, stream, p, s, n);
-  }
+  bool virtualIdx = false;
+  const bool rowSpace = prepare_filter(device, stream, p, indexVector, pred, n, numForeignTables, baseCounts, &virtualIdx);
   FastOperands f;
   const bool fast = !is_wide(p.a.kind) && indexVector != nullptr && fast_operands(p, f, true);
-  if (fast && !onePass && numForeignTables == 0 && baseCounts == nullptr)
+  if (fast && numForeignTables == 0 && baseCounts == nullptr)
     journal_filter(device, indexVector, &f, p.a.length, n, decoded);
   else
     journal_filter(device, indexVector, nullptr, 0, 0);
@@ -1923,144 +1824,8 @@ static int run_filter(const InputVector *ins, int arity, uint32_t *indexVector, 
     DeferLock lock(device);
     run_compaction(indexVector);
   }
-  if (fast && !onePass) {
-    // two-phase path: predicate + tile counts, scan, chain-free compaction of the index vector and
-    // of every RecordID vector
-    f.pad = static_cast<int>(reinterpret_cast<uintptr_t>(pred) & 3);
-    const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
-    const int tiles = static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
-    const int passes = 1 + numForeignTables;
-    // layout: [total, error, tickets[passes], pad][tileCounts][tileOffsets + 1][loaded x passes][one partial count per workgroup]
-    const size_t head = 64;
-    constexpr int kPredGridCap = 256 * 16;
-    static_assert(kPredGridCap <= kPinnedWords, "the partial counts are read back in one copy");
-    const int predGrid = capped_grid(tiles, kPredGridCap);
-    const size_t words = static_cast<size_t>(tiles) * (2 + passes) + 1 + static_cast<size_t>(predGrid);
-    auto wsBuf = std::make_shared<StreamBuffer>(head + 4 * words, stream);
-    uint32_t *w = wsBuf->as<uint32_t>();
-    uint32_t *total = w, *error = w + 1;
-    unsigned int *tickets = w + 2;
-    uint32_t *tileCounts = w + 16, *tileOffsets = tileCounts + tiles, *loaded = tileOffsets + tiles + 1;
-    hip_check(hipMemsetAsync(w, 0, head + 4 * words, stream), "hipMemsetAsync");  // one fill: head, counts, flags
-    if (virtualIdx) f.idx = nullptr;  // rows = position
-    const bool lazy = numForeignTables == 0 && journal_is_valid(device, indexVector);
-    // ARES_FILTER_LAZY_SCAN=0: the tile offsets are computed at once, as before round 3
-    static EnvSwitch<bool> lazyScan("ARES_FILTER_LAZY_SCAN", [](const char *e) { return !(e && e[0] == '0'); });
-    const bool scanLater = lazy && lazyScan.get();
-    uint32_t *partials = loaded + static_cast<size_t>(tiles) * passes;
-    FilterCheck check;
-    check.begin(f, p.a.length, n, tiles, predGrid, pred, stream);
-    ARES_LAUNCH("filter_pred_kernel", filter_pred_kernel, predGrid, kBlock, stream, f, pred, tileCounts, n, tiles,
-                scanLater ? partials : nullptr);
-    check.after_kernel();
-    if (!scanLater) ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, stream, tileCounts, tileOffsets, tiles, total);
-    if (lazy) {
-      // The count is known; the compaction waits until somebody needs the compacted vector — a
-      // HashReduce that re-derives the survivors from the journal never does.
-      uint32_t result[2] = {0, 0};
-      if (scanLater) {
-        uint32_t parts[kPredGridCap];
-        read_back_u32(partials, parts, predGrid, stream);
-        for (int b = 0; b < predGrid; b++) result[0] += parts[b];
-      } else {
-        read_back_u32(total, result, 2, stream);
-      }
-      PendingCompact c;
-      c.device = device;
-      c.stream = stream;
-      c.idx = indexVector;
-      c.pred = pred;
-      c.n = n;
-      c.pad = f.pad;
-      c.tiles = tiles;
-      c.virtualIdx = virtualIdx;
-      c.ws = wsBuf;
-      c.ticket = tickets;
-      c.error = error;
-      c.tileOffsets = tileOffsets;
-      c.loaded = loaded;
-      if (scanLater) {
-        c.tileCounts = tileCounts;
-        c.total = total;
-      }
-      check.finish(result[0]);
-      DeferLock lock(device);
-      t_state->compactions[indexVector] = c;
-      return static_cast<int>(result[0]);
-    }
-    const int cgrid = capped_grid((tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
-    if (virtualIdx) f.idx = nullptr;
-    mem_note_write(device, indexVector, 4ull * static_cast<size_t>(n));
-    for (int t = 0; t < numForeignTables; t++) mem_note_write(device, recordIDVectors[t], 8ull * static_cast<size_t>(n));
-    for (int pass = 0; pass < passes; pass++) {
-      CompactWorkspace cw;
-      cw.ticket = tickets + pass;
-      cw.error = error;
-      cw.tileOffsets = tileOffsets;
-      cw.loaded = loaded + static_cast<size_t>(tiles) * pass;
-      if (pass == 0 && virtualIdx)
-        ARES_LAUNCH("filter_compact_kernel<iota>", (filter_compact_kernel<uint32_t, true>), cgrid, kBlock, stream, pred, indexVector,
-                    0u, f.pad, cw, n, tiles);
-      else if (pass == 0)
-        ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, stream, pred, indexVector, 0u,
-                    f.pad, cw, n, tiles);
-      else
-        ARES_LAUNCH("filter_compact_kernel<rid>", (filter_compact_kernel<uint64_t, false>), cgrid, kBlock, stream, pred,
-                    reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), 0u, f.pad, cw, n, tiles);
-    }
-    uint32_t result[2] = {0, 0};  // {survivors, error}
-    read_back_u32(total, result, 2, stream);
-    check.finish(result[0]);
-    if (result[1]) throw AlgorithmError("ERROR: filter: compaction wait timed out");
-    return static_cast<int>(result[0]);
-  }
-  if (virtualIdx) {  // the one-pass kernels read the index vector: write it now
-    DeferLock lock(device);
-    launch_init_index(indexVector, 0, n, stream);
-  }
-  mem_note_write(device, indexVector, 4ull * static_cast<size_t>(n));
-  for (int t = 0; t < numForeignTables; t++) mem_note_write(device, recordIDVectors[t], 8ull * static_cast<size_t>(n));
-  int numTiles = static_cast<int>((static_cast<int64_t>(n) + kFilterTile - 1) / kFilterTile);
-  int fastTiles = 0;
-  if (fast) {
-    f.pad = static_cast<int>(reinterpret_cast<uintptr_t>(pred) & 3);
-    const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
-    fastTiles = static_cast<int>((numQuads + kBlock * kFQ - 1) / (kBlock * kFQ));
-  }
-  const int passes = 1 + numForeignTables;
-  const size_t passBytes = 16 + sizeof(uint64_t) * static_cast<size_t>(numTiles);
-  StreamBuffer wsBuf(passBytes * passes, stream);
-  hip_check(hipMemsetAsync(wsBuf.get(), 0, passBytes * passes, stream), "hipMemsetAsync");
-  const int grid = capped_grid(numTiles);
-  uint32_t *totalDev = nullptr;
-  for (int pass = 0; pass < passes; pass++) {
-    uint8_t *base = wsBuf.as<uint8_t>() + passBytes * pass;
-    ScanWorkspace ws;
-    ws.ticket = reinterpret_cast<unsigned int *>(base);
-    ws.total = reinterpret_cast<uint32_t *>(base + 4);
-    ws.error = reinterpret_cast<uint32_t *>(wsBuf.as<uint8_t>() + 8);  // shared by all passes
-    ws.status = reinterpret_cast<uint64_t *>(base + 16);
-    if (pass == 0) {
-      totalDev = ws.total;
-      if (is_wide(p.a.kind)) {
-        ARES_LAUNCH("filter_kernel<2>", filter_kernel<2>, grid, kBlock, stream, p, pred, indexVector,
-                           static_cast<uint64_t *>(nullptr), ws, n, numTiles);
-      } else if (fast) {
-        ARES_LAUNCH("filter_fast_kernel", filter_fast_kernel, capped_grid(fastTiles, (f.debug & 4) ? 256 * 3 : 256 * 5), kBlock, stream, f, pred,
-                    indexVector, ws, n, fastTiles);
-      } else {
-        ARES_LAUNCH("filter_kernel<0>", filter_kernel<0>, grid, kBlock, stream, p, pred, indexVector,
-                    static_cast<uint64_t *>(nullptr), ws, n, numTiles);
-      }
-    } else {
-      ARES_LAUNCH("filter_kernel<1>", filter_kernel<1>, grid, kBlock, stream, p, pred, indexVector,
-                  reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), ws, n, numTiles);
-    }
-  }
-  uint32_t result[2] = {0, 0};  // {survivors, error}
-  read_back_u32(totalDev, result, 2, stream);
-  if (result[1]) throw AlgorithmError("ERROR: filter: inter-tile scan timed out");
-  return static_cast<int>(result[0]);
+  if (fast) return run_filter_two_phase(device, stream, f, indexVector, pred, n, recordIDVectors, numForeignTables, virtualIdx);
+  return run_filter_generic(device, stream, p, isArray ? &arr : nullptr, indexVector, pred, n, recordIDVectors, numForeignTables);
 }
 
 // ---------------------------------------------------------------------------------------------

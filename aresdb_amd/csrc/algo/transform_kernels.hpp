@@ -620,7 +620,7 @@ __device__ __forceinline__ void issue_values(const FastOperands &f, const uint32
 #pragma unroll
       for (int j = 0; j < 4; j++) vals[q][j] = f.akind == K_I32 ? static_cast<uint32_t>(static_cast<int32_t>(static_cast<int8_t>(raw[j]))) : raw[j];
     } else if (rows[q][1] == r0 + 1 && rows[q][2] == r0 + 2 && rows[q][3] == r0 + 3) {
-      if (f.debug & 128) {  // streaming loads for a column that is read once (set by run_filter_rows)
+      if (f.streaming) {  // a column that is read once (set by run_filter_rows)
         typedef uint32_t V4 __attribute__((ext_vector_type(4)));
         typedef V4 V4a __attribute__((aligned(4)));
         const V4 v = __builtin_nontemporal_load(reinterpret_cast<const V4a *>(f.vals + r0));
@@ -817,121 +817,9 @@ __global__ __launch_bounds__(kBlock, 3) void transform_multi_kernel(MultiJobs jo
 }
 
 // ---------------------------------------------------------------------------------------------
-// fast filter: predicate + stable in-place compaction, 8192-row tiles
-// ---------------------------------------------------------------------------------------------
-// One returning atomic on the ticket word hands out a tile; a single word sustains ~90 tickets per
-// microsecond on this chip, so the tile must be large (8192 rows -> > 700 G rows/s) for the ticket
-// not to cap the kernel.  Survivors are ranked with a packed wavefront scan, staged in LDS in
-// final order and written back with fully coalesced stores.
-constexpr int kFQ = 8;
-constexpr int kFastTile = kBlock * 4 * kFQ;
-
-__global__ __launch_bounds__(kBlock) void filter_fast_kernel(FastOperands f, uint8_t *pred, uint32_t *idx,
-                                                             ScanWorkspace ws, int n, int numTiles) {
-  __shared__ uint32_t sOut[kFastTile];
-  __shared__ uint32_t sCounts[kFQ * kWaves];
-  __shared__ int sTile;
-  __shared__ uint32_t sBase, sTileCount;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  DVal y;
-  y.bits = f.bbits;
-  y.ok = f.bok;
-  y = cvt32(y, f.bkind, f.I);
-  for (int iter = 0;; iter++) {
-    __syncthreads();  // LDS of the previous tile is free again
-    if (threadIdx.x == 0)
-      sTile = (f.debug & 4) ? static_cast<int>(blockIdx.x + iter * gridDim.x) : static_cast<int>(atomicAdd(ws.ticket, 1u));
-    __syncthreads();
-    const int tile = sTile;
-    if (tile >= numTiles) break;
-    const int64_t tq = static_cast<int64_t>(tile) * (kBlock * kFQ);
-
-    uint32_t rows[kFQ][4], vals[kFQ][4], okb[kFQ];
-    load_quads<kFQ>(f, tq + threadIdx.x, n, rows, vals, okb);
-    uint32_t keep = 0;
-#pragma unroll
-    for (int q = 0; q < kFQ; q++) {
-      const int64_t i0 = (tq + threadIdx.x + static_cast<int64_t>(q) * kBlock) * 4 - f.pad;
-      uint32_t kb = 0;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const int64_t i = i0 + j;
-        if (i >= 0 && i < n) {
-          kb |= compare_fast(f, vals[q][j], (okb[q] >> j) & 1u, y) << j;  // result validity is ignored (functor.hpp:903-915)
-        }
-      }
-      keep |= kb << (4 * q);
-      const uint32_t bytes = (kb & 1u) | ((kb & 2u) << 7) | ((kb & 4u) << 14) | ((kb & 8u) << 21);
-      if (i0 >= 0 && i0 + 3 < n) {
-        *reinterpret_cast<uint32_t *>(pred + i0) = bytes;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          if (i0 + j >= 0 && i0 + j < n) pred[i0 + j] = static_cast<uint8_t>((kb >> j) & 1u);
-      }
-    }
-    // Every index-vector word of this tile has been consumed (the predicate depends on it) before
-    // the tile's count becomes visible: later tiles only overwrite our input range after that.
-
-    // rank of every survivor inside its wavefront: ballots + mbcnt (pure VALU/SALU, no cross-lane
-    // traffic); position order inside the tile is (quad, lane, j)
-    uint32_t lanePrefix[kFQ];
-#pragma unroll
-    for (int q = 0; q < kFQ; q++) {
-      uint32_t before = 0, total = 0;
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint64_t m = __ballot((keep >> (4 * q + j)) & 1u);
-        before += __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u));
-        total += static_cast<uint32_t>(__popcll(m));
-      }
-      lanePrefix[q] = before;
-      if (lane == 0) sCounts[q * kWaves + wave] = total;
-    }
-    __syncthreads();
-    if (wave == 0) {
-      // exclusive scan of the kFQ * kWaves (= 32) partial counts in position order
-      uint32_t c = lane < kFQ * kWaves ? sCounts[lane] : 0u;
-      uint32_t incl = c;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-      }
-      const uint32_t tileCount = __shfl(incl, 63);
-      if (lane == 0) st_status(ws.status + tile, (tile == 0 ? kFlagInclusive : kFlagAggregate) | tileCount);
-      uint32_t exclusive = 0;
-      if (tile > 0 && !(f.debug & 1)) {
-        exclusive = static_cast<uint32_t>(lookback_wave(ws.status, tile, lane, ws.error));
-        if (lane == 0) st_status(ws.status + tile, kFlagInclusive | (exclusive + tileCount));
-      }
-      if (f.debug & 1) exclusive = static_cast<uint32_t>(tile) * 7000u;
-      if (lane < kFQ * kWaves) sCounts[lane] = incl - c;
-      if (lane == 0) {
-        sBase = exclusive;
-        sTileCount = (f.debug & 2) ? 0u : tileCount;
-        if (tile == numTiles - 1) *ws.total = exclusive + tileCount;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < kFQ; q++) {
-      uint32_t at = sCounts[q * kWaves + wave] + lanePrefix[q];
-      const uint32_t kb = (keep >> (4 * q)) & 0xFu;
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if ((kb >> j) & 1u) sOut[at++] = rows[q][j];
-    }
-    __syncthreads();
-    const uint32_t count = sTileCount, gbase = sBase;
-    for (uint32_t k = threadIdx.x; k < count; k += kBlock) idx[gbase + k] = sOut[k];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // two-phase filter: predicate + per-tile counts, scan, in-place compaction without a chain
 // ---------------------------------------------------------------------------------------------
-// The one-pass kernel above is bound by the latency of its per-tile chain (index -> column loads,
+// A one-pass kernel is bound by the latency of its per-tile chain (index -> column loads,
 // ranking, look-back, staging).  Splitting it removes every inter-tile dependency from the hot
 // loops: (1) a streaming kernel evaluates the predicate, writes the predicate bytes and one
 // survivor count per 4096-row tile; (2) a single small workgroup turns the counts into offsets;
@@ -1059,12 +947,7 @@ __global__ __launch_bounds__(kBlock) void filter_rows_kernel(FastOperands f, Fas
 #pragma unroll
     for (int q = 0; q < kPQ; q++) k1 |= kbs[q] << (4 * q);
     k1 &= alive;
-    if (f.debug & 8) {  // (experiment: pairs of lanes store one dword instead of two shorts)
-      const uint32_t other = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(k1), 0xB1, 0xF, 0xF, true));
-      if (!(lane & 1)) reinterpret_cast<uint32_t *>(bitsOut)[word >> 1] = k1 | (other << 16);
-    } else {
-      bitsOut[word] = static_cast<uint16_t>(k1);
-    }
+    bitsOut[word] = static_cast<uint16_t>(k1);
     mine += __popc(k1);
     if (TWO) {
       compare_tile<kPQ>(g, vals, okb, in, z, kbs2);

@@ -263,17 +263,9 @@ hipError_t device_state(int device, DeviceState **out) {
   if (device < 0 || device >= kMaxDevices) return hipErrorInvalidDevice;
   DeviceState &st = g_devices[device];
   std::call_once(st.once, [&] {
-    // ARES_MEM_FILL_PRIORITY=low puts the fills of parked blocks on a lowest-priority stream.  Measured:
-    // the scan kernel gains 0-3 %, but the first process on a box now and then takes twice as long per
-    // step with it (3 of 5 fresh boxes) — so the default is an ordinary stream.
-    int priority = 0;
-    const char *e = getenv("ARES_MEM_FILL_PRIORITY");
-    if (e && strcmp(e, "low") == 0) {
-      int least = 0, greatest = 0;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess) priority = least;
-      else (void)hipGetLastError();
-    }
-    st.initError = hipStreamCreateWithPriority(&st.allocStream, hipStreamNonBlocking, priority);
+    // The fills of parked blocks run on an ordinary stream: on a lowest-priority one the scan kernel gained 0-3 %, but the
+    // first process on a machine now and then took twice as long per step (3 of 5 fresh machines).
+    st.initError = hipStreamCreateWithFlags(&st.allocStream, hipStreamNonBlocking);
     if (st.initError == hipSuccess) st.initError = hipStreamCreateWithFlags(&st.freshStream, hipStreamNonBlocking);
     size_t freeB = 0, totalB = 0;
     if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) st.cacheCapBytes = totalB / 4;
@@ -491,14 +483,7 @@ hipError_t pool_alloc(DeviceState *st, void **p, size_t bytes, bool zero) {
       std::lock_guard<std::mutex> lock(st->mu);
       st->driverAllocs++;
     }
-    // ARES_MEM_POOL_ALLOC=1 (experiment for the next round): fresh blocks from the stream-ordered pool (see
-    // libalgorithm's ARES_TEMP_POOL_ALLOC); nothing is ever freed into that pool
-    static const bool poolAlloc = [] {
-      const char *v = getenv("ARES_MEM_POOL_ALLOC");
-      return v && v[0] == '1';
-    }();
-    hipError_t e = poolAlloc ? hipMallocAsync(&ptr, rounded, st->freshStream) : hipMalloc(&ptr, rounded);
-    if (e == hipSuccess && poolAlloc) e = hipStreamSynchronize(st->freshStream);
+    hipError_t e = hipMalloc(&ptr, rounded);
     if (e != hipSuccess) {  // out of memory: give both libraries' caches back and retry once
       (void)hipGetLastError();
       {

@@ -1,5 +1,5 @@
-"""profiles/r<N>_kernel_stats_summary.md from the rocprofv3 `--kernel-trace --stats` CSVs that tools/gpu_r<N>_evidence.sh leaves
-(copied to profiles/r<N>_<tag>_kernel_stats_rocprofv3.csv):  [ARES_ROUND=5] python tools/kernel_stats_summary.py"""
+"""profiles/r<N>_kernel_stats_summary.md from the rocprofv3 `--kernel-trace --stats` CSVs of a round's profiling runs
+(kept as profiles/r<N>_<tag>_kernel_stats_rocprofv3.csv):  [ARES_ROUND=5] python tools/kernel_stats_summary.py"""
 import csv
 import os
 
