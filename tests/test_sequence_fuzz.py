@@ -32,6 +32,32 @@ MEASURES = [  # (column, aggregate, measure data type, bytes, numpy type)
 ]
 
 
+# The "edges" profile: fixed lookup tables that spread the programs' small draws (u in [0, 12), i in [-6, 7), d in [0, 3)) over
+# the full range of the columns' types, per stored type.  Looked up, never drawn: a seed stays the same program.
+_EDGE_TABLES = {
+    ("u", np.uint32): [0, 1, 2 ** 31 - 1, 2 ** 31, 2 ** 31 + 1, 3 * 2 ** 30, 2 ** 32 - 2, 2 ** 32 - 1, 2 ** 24 + 1, 65536, 2 ** 31 + 86400, 3000000000],
+    ("u", np.uint16): [0, 1, 255, 256, 32767, 32768, 32769, 65534, 65535, 3600, 40000, 20864],
+    ("i", np.int32): [-2 ** 31, -2 ** 31 + 1, -2 ** 30, -65537, -129, -1, 0, 1, 128, 65536, 2 ** 30, 2 ** 31 - 2, 2 ** 31 - 1],
+    ("i", np.int16): [-32768, -32767, -257, -129, -128, -1, 0, 1, 127, 128, 255, 32766, 32767],
+    ("i", np.int8): [-128, -127, -100, -3, -2, -1, 0, 1, 2, 3, 100, 126, 127],
+    ("d", np.uint32): [0, 2 ** 31, 2 ** 32 - 1],
+    ("d", np.uint8): [0, 128, 255],
+}
+_EDGE_LOW = {"u": 0, "i": -6, "d": 0}
+
+
+def _edge_values(col, small):
+    """the column's small draws mapped into the full range of its stored type"""
+    small = np.asarray(small)
+    table = np.array(_EDGE_TABLES[(col, small.dtype.type)], np.int64).astype(small.dtype)
+    return table[np.clip(small.astype(np.int64) - _EDGE_LOW[col], 0, len(table) - 1)]
+
+
+def _edge_float(f):
+    """exact quarters -> values that are not: every sum of them rounds"""
+    return (np.asarray(f, np.float32) * np.float32(0.1) + np.float32(1.0 / 3.0)).astype(np.float32)
+
+
 def _d2h(be, ptr, nbytes, stream):
     return H.download(be, ptr, nbytes, stream)
 
@@ -50,7 +76,10 @@ class Program:
         their order (ascending 64-bit hash) — a Sort that was only defined (sort_reduce_fused.hip) has to materialise, a
         Reduce that consumed it has to be replayed; "eager" — the host looks at the batch's dimension rows before every
         reduction, so they exist when Sort is called (what a join or a generic expression leads to as well): Sort + Reduce over
-        materialised vectors (fused_sort_reduce_vectors: the wide layout).  None draws from the program's random stream: a
+        materialised vectors (fused_sort_reduce_vectors: the wide layout); "edges" — the values of u, i, d and the constants they are
+        compared with are looked up in fixed tables that reach the extremes of their types (u around 2^31 and 2^32 - 1, i at
+        INT32_MIN / INT32_MAX, narrow columns at full range), f is no longer a multiple of a quarter: signedness, widening,
+        wrap-around and truncation into 2-byte slots through the whole call sequence.  None draws from the program's random stream: a
         seed is the same program in every profile."""
         self.seed = seed
         self.profile = tuple(profile)
@@ -128,6 +157,10 @@ class Program:
                 types.update({"u": abi.Uint16, "i": abi.Int16 if self.seed % 2 else abi.Int8, "d": abi.Uint8})
                 raw["u"], raw["d"] = raw["u"].astype(np.uint16), raw["d"].astype(np.uint8)
                 raw["i"] = raw["i"].astype(np.int16 if self.seed % 2 else np.int8)
+            if "edges" in self.profile:
+                small = {k: raw[k] for k in ("u", "i", "d")}
+                raw.update({k: _edge_values(k, v) for k, v in small.items()})
+                raw["f"] = _edge_float(raw["f"])
             valid = {k: (rng.random(n) > 0.05) if nulls and rng.random() < 0.8 else None for k in raw}
             cols = {k: H.Column(be, types[k], raw[k], valid=valid[k]) for k in raw}
             idx, pred = H.Buf(be, nbytes=4 * n), H.Buf(be, nbytes=n)
@@ -145,10 +178,14 @@ class Program:
                 if kind < 0.75:    # fast shape: column <cmp> constant
                     col = ["ts", "u", "i", "d", "f"][int(rng.integers(0, 5))]
                     if col == "f":
-                        const = H.const_float(float(rng.integers(-150, 150)))
+                        cf = float(rng.integers(-150, 150))
+                        const = H.const_float(float(_edge_float(cf)) if "edges" in self.profile else cf)
                     else:
                         lo, hi = {"ts": (0, 86400 * 2), "u": (0, 12), "i": (-6, 7), "d": (0, 3)}[col]
-                        const = H.const_int(int(lo + (hi - lo) * rng.random() * 1.2))
+                        ci = int(lo + (hi - lo) * rng.random() * 1.2)
+                        if "edges" in self.profile and col != "ts":  # (integer constants are int32 in the ABI: the table value's low 32 bits)
+                            ci = int(np.int64(_edge_values(col, np.array([ci]).astype(small[col].dtype))[0]).astype(np.int32))
+                        const = H.const_int(ci)
                     size = be.call("BinaryFilter", cols[col].input(), const, idx.ptr, pred.ptr, size, None, 0, None, 0,
                                    CMPS[int(rng.integers(0, 6))], stream, 0)
                 elif kind < 0.9:   # generic shape: two columns
@@ -166,6 +203,8 @@ class Program:
                 obs.append(("index", b, _d2h(be, idx.ptr, 4 * size, stream).tobytes()))
             if size and rng.random() < 0.06:  # a column changes under the query between filter and projection
                 fresh = rng.integers(0, 12, n).astype(raw["u"].dtype)
+                if "edges" in self.profile:
+                    fresh = _edge_values("u", fresh)
                 vp = cols["u"].vp
                 H.upload(be, vp.BasePtr + vp.ValuesOffset, fresh, stream)
             # result buffers: capacity for resultSize + size (+ 12.5 %), previous results carried over
@@ -320,6 +359,33 @@ def test_random_programs_sorting_rows_that_exist(profile):
         p = Program(seed, profile)
         want = p.run(oracle)
         _same(p.run(hip, expect=want), want, seed)
+
+
+EDGE_PROFILES = [("edges",), ("edges", "narrow"), ("edges", "sort"), ("edges", "drift"), ("edges", "prealloc"), ("edges", "sort", "narrow"),
+                 ("edges", "sort", "eager")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("chunk", range(4))
+def test_random_programs_at_the_edges_of_the_types_match_the_oracle(chunk):
+    """56 programs in the "edges" profiles (a list of their own: PROFILES and the programs the tests above pair with each seed stay
+    as they were): signed / unsigned comparisons, 1- and 2-byte widening, wrapping sums, keys with their top bit set, 32-bit
+    results truncated into 2-byte slots, through the deferred / fused / sorted call sequences."""
+    hip, oracle = H.hip_backend(), H.oracle_backend()
+    for k, seed in enumerate(range(4000 + chunk, 4056, 4)):
+        p = Program(seed, EDGE_PROFILES[(k + chunk) % len(EDGE_PROFILES)])
+        want = p.run(oracle)
+        _same(p.run(hip, expect=want), want, seed)
+
+
+def test_random_programs_at_the_edges_reference_build_matches_the_oracle():
+    """The "edges" programs on the reference's own HOST build."""
+    if not H.have_ref():
+        pytest.skip("reference HOST build absent")
+    ref, oracle = H.ref_backend(), H.oracle_backend()
+    for k, seed in enumerate(range(4000, 4028)):
+        p = Program(seed, EDGE_PROFILES[k % len(EDGE_PROFILES)])
+        _same(p.run(ref), p.run(oracle), seed)
 
 
 def test_random_programs_reference_build_matches_the_oracle():
