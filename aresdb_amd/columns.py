@@ -24,6 +24,9 @@ class DeviceColumn:
             vbytes = np.packbits(values.astype(bool), bitorder="little")
         elif data_type == abi.GeoPoint:  # (n, 2) float32 {lat, long}
             vbytes = np.ascontiguousarray(values.astype(np.float32)).reshape(-1).view(np.uint8)
+        elif data_type == abi.UUID:  # (n, 16) uint8 or (n, 2) uint64 {p1, p2}
+            vbytes = np.ascontiguousarray(values).reshape(len(values), -1).view(np.uint8).reshape(-1)
+            assert len(vbytes) == 16 * len(values)
         else:
             vbytes = np.ascontiguousarray(values.astype(_NP_OF[data_type])).view(np.uint8)
         cbytes = np.zeros(0, np.uint8) if counts is None else np.asarray(counts, np.uint32).view(np.uint8)

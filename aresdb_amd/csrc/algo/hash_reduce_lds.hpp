@@ -27,6 +27,21 @@ int hash_reduce_lds(int device, const DimensionVector &inputKeys, const uint8_t 
 constexpr int kFusedCols = 10, kFusedFilters = 6, kFusedDims = 8;
 constexpr int kGenericFusedDims = 4;
 constexpr int kExtensionFilters = 4;  // AresFusedQuery::filters (include/ares_extensions.h)
+// Sort + Reduce over rows that exist (fused_sort_reduce_vectors) also takes slots of 8 and 16 bytes (Int64 / Uint64 / GeoPoint,
+// UUID).  Its generated scan holds four rows per lane in registers: up to eight dimensions of 4 / 2 / 1 bytes as before, and —
+// once a slot is wider than that — up to kSortVectorValueBytes value bytes per row (the eight-dimension shape's footprint).
+// ONE predicate for Sort (which defines itself lazily), Reduce (which consumes the definition) and the generator: a layout
+// beyond it keeps the real Sort + Reduce.
+constexpr int kSortVectorValueBytes = 32;
+inline bool sort_vector_layout_supported(const uint8_t numDimsPerDimWidth[NUM_DIM_WIDTH]) {
+  int nd = 0, valueBytes = 0;
+  for (int w = 0; w < NUM_DIM_WIDTH; w++) {
+    nd += numDimsPerDimWidth[w];
+    valueBytes += numDimsPerDimWidth[w] << (NUM_DIM_WIDTH - 1 - w);
+  }
+  const bool wide = numDimsPerDimWidth[0] || numDimsPerDimWidth[1];
+  return nd >= 1 && nd <= kFusedDims && (!wide || valueBytes <= kSortVectorValueBytes);
+}
 struct FusedColumn {
   const uint32_t *vals;
   const uint8_t *nulls;

@@ -802,8 +802,10 @@ void gen_row_hash(std::ostringstream &o, const SlotLayout &L, const std::functio
     << indent << "  " << out << " = g;\n" << indent << "}\n";
 }
 // lo64(murmur3_x64_128) (seed 0) of the packed row — Murmur128Stream of dim_layout.hpp, query/utils.cu:157-241 — with the
-// same naming of values and validity bits as gen_row_hash; writes the statements that leave the hash in the u64 `out`
-void gen_row_hash64(std::ostringstream &o, const SlotLayout &L, const std::function<std::string(int)> &val,
+// same naming of values and validity bits as gen_row_hash; writes the statements that leave the hash in the u64 `out`.
+// `val(d, k)` names 32-bit word k of dimension d's value: slots of 8 and 16 bytes are fields of two and four words (widths
+// descend from 16, so such a field starts on a word of the packed row and its words go into the murmur lanes as they are)
+void gen_row_hash64(std::ostringstream &o, const SlotLayout &L, const std::function<std::string(int, int)> &val,
                     const std::function<std::string(int)> &okb, const std::string &out, const char *indent) {
   const int total = L.valueBytes + L.nd, words = (total + 3) / 4;
   std::vector<std::string> w(static_cast<size_t>(words));
@@ -813,7 +815,8 @@ void gen_row_hash64(std::ostringstream &o, const SlotLayout &L, const std::funct
     const std::string term = sh ? "(" + e + " << " + std::to_string(sh) + ")" : e;
     x = x.empty() ? term : x + " | " + term;
   };
-  for (int d = 0; d < L.nd; d++) add(L.off[d], val(d));
+  for (int d = 0; d < L.nd; d++)
+    for (int k = 0; 4 * k < L.width[d] || k == 0; k++) add(L.off[d] + 4 * k, val(d, k));
   for (int d = 0; d < L.nd; d++) add(L.valueBytes + d, okb(d));
   auto lane64 = [&](int firstWord) {  // 8 row bytes from 32-bit word `firstWord` on, as a u64 expression ("" = none left)
     if (firstWord >= words) return std::string();
@@ -1011,7 +1014,7 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
       o << "#pragma unroll\n  for (int j = 0; j < 4; j++) {\n";
       if (sort64) {  // the record's second word holds the hash's upper half (its top bits choose the partition), the fourth the lower
         o << "    u64 h64;\n";
-        gen_row_hash64(o, SL, [](int d) { return "xv" + std::to_string(d) + "[j]"; }, [](int d) { return "xo" + std::to_string(d) + "[j]"; },
+        gen_row_hash64(o, SL, [](int d, int) { return "xv" + std::to_string(d) + "[j]"; }, [](int d) { return "xo" + std::to_string(d) + "[j]"; },
                        "h64", "    ");
         o << "    hh[j] = (u32)(h64 >> 32); cw[j] = (u32)h64;\n";
       } else {
@@ -1039,33 +1042,55 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
 // rowBase, vals[nd] = the measures at rowBase.  Records carry the whole value: {row, hash, lo, hi}.
 // sort64: the Sort + Reduce path over materialised vectors (sort_reduce_fused.hip): records {row, hash64 >> 32, the 4-byte value,
 // (u32)hash64} keyed by lo64(murmur3_x64_128) of the packed row, partition = top bits of the 64-bit hash; up to eight dimensions.
-// widths (sort64 only): the dimension slots' bytes in vector order (4 / 2 / 1, descending); null: all four bytes
+// widths (sort64 only): the dimension slots' bytes in vector order (16 / 8 / 4 / 2 / 1, descending); null: all four bytes.
+// A row's values live in 32-bit words of `Raw::v`: one word per slot of 4, 2 or 1 bytes, two per 8-byte slot (Int64, Uint64,
+// GeoPoint), four per 16-byte slot (UUID) — at most kSortVectorValueBytes per row (sort_vector_layout_supported), which is
+// what four rows per lane leave of 128 VGPRs.
 std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, const int *widths = nullptr) {
   if (nd < 1 || nd > (sort64 ? kFusedDims : kGenericFusedDims) || (vw != 4 && vw != 8) || (sort64 && vw != 4)) return "";
-  int width[kFusedDims] = {4, 4, 4, 4, 4, 4, 4, 4};
-  bool narrow = false;
+  int width[kFusedDims] = {4, 4, 4, 4, 4, 4, 4, 4}, wb[kFusedDims] = {0, 1, 2, 3, 4, 5, 6, 7};
+  bool narrow = false, wide = false;
+  int valueBytes = 0, nw = 0;
   for (int d = 0; widths && d < nd; d++) {
-    if ((widths[d] != 4 && widths[d] != 2 && widths[d] != 1) || (d && widths[d] > widths[d - 1]) || !sort64) return "";
+    if ((widths[d] != 16 && widths[d] != 8 && widths[d] != 4 && widths[d] != 2 && widths[d] != 1) || (d && widths[d] > widths[d - 1]) || !sort64)
+      return "";
     width[d] = widths[d];
     narrow = narrow || widths[d] != 4;
+    wide = wide || widths[d] > 4;
+    valueBytes += widths[d];
+    wb[d] = nw;
+    nw += widths[d] > 4 ? widths[d] / 4 : 1;
   }
+  if (wide && valueBytes > kSortVectorValueBytes) return "";
   std::ostringstream o;
   const int mq = vw / 4;
   o << kPrelude << (sort64 ? kPrelude64 : "") << args_text()
-    << "#define ND " << nd << "\n#define MQ " << mq << "\n#define PB " << partBits << "\n#define NP " << (1 << partBits) << "\n"
-       "struct Raw { u32 v[ND][4]; u32 ok[ND]; u32 m[MQ * 4]; };\n"
-       "__device__ __forceinline__ void load_full(Raw &r, const Args &a, u32 i0) {\n";
-  if (narrow) {  // (slot by slot: a 2-byte slot's four rows are one 8-byte load, a 1-byte slot's one 4-byte load)
+    << "#define ND " << nd << "\n#define MQ " << mq << "\n#define PB " << partBits << "\n#define NP " << (1 << partBits) << "\n";
+  if (wide) o << "#define NW " << nw << "\nstruct Raw { u32 v[NW][4]; u32 ok[ND]; u32 m[MQ * 4]; };\n";
+  else o << "struct Raw { u32 v[ND][4]; u32 ok[ND]; u32 m[MQ * 4]; };\n";
+  o << "__device__ __forceinline__ void load_full(Raw &r, const Args &a, u32 i0) {\n";
+  if (narrow) {  // (slot by slot: a 2-byte slot's four rows are one 8-byte load, a 1-byte slot's one 4-byte load, an 8-byte
+                 // slot's two 16-byte loads, a 16-byte slot's four — `rowBase` is any row: none of them assumes more than the
+                 // slot's own alignment)
     for (int d = 0; d < nd; d++) {
-      if (width[d] == 4)
-        o << "  { const PU32x4 t = *reinterpret_cast<const PU32x4 *>(a.vals[" << d << "] + i0); r.v[" << d << "][0] = t.v[0]; r.v[" << d
-          << "][1] = t.v[1]; r.v[" << d << "][2] = t.v[2]; r.v[" << d << "][3] = t.v[3]; }\n";
+      const int v = wb[d];
+      if (width[d] > 4) {
+        const int q = width[d] / 4;  // words per row: load k holds words [4k, 4k + 4) of the quad's 4 * q
+        o << "  {\n    const PU32x4 *p = reinterpret_cast<const PU32x4 *>(reinterpret_cast<const u8 *>(a.vals[" << d << "]) + " << width[d] << "ull * i0);\n";
+        for (int k = 0; k < q; k++) o << "    const PU32x4 t" << k << " = p[" << k << "];\n";
+        o << "   ";
+        for (int k = 0; k < q; k++)
+          for (int e = 0; e < 4; e++) o << " r.v[" << v + (4 * k + e) % q << "][" << (4 * k + e) / q << "] = t" << k << ".v[" << e << "];";
+        o << "\n  }\n";
+      } else if (width[d] == 4)
+        o << "  { const PU32x4 t = *reinterpret_cast<const PU32x4 *>(a.vals[" << d << "] + i0); r.v[" << v << "][0] = t.v[0]; r.v[" << v
+          << "][1] = t.v[1]; r.v[" << v << "][2] = t.v[2]; r.v[" << v << "][3] = t.v[3]; }\n";
       else if (width[d] == 2)
-        o << "  { const PU32x2 t = *reinterpret_cast<const PU32x2 *>(reinterpret_cast<const u8 *>(a.vals[" << d << "]) + 2ull * i0); r.v[" << d
-          << "][0] = t.v[0] & 0xFFFFu; r.v[" << d << "][1] = t.v[0] >> 16; r.v[" << d << "][2] = t.v[1] & 0xFFFFu; r.v[" << d << "][3] = t.v[1] >> 16; }\n";
+        o << "  { const PU32x2 t = *reinterpret_cast<const PU32x2 *>(reinterpret_cast<const u8 *>(a.vals[" << d << "]) + 2ull * i0); r.v[" << v
+          << "][0] = t.v[0] & 0xFFFFu; r.v[" << v << "][1] = t.v[0] >> 16; r.v[" << v << "][2] = t.v[1] & 0xFFFFu; r.v[" << v << "][3] = t.v[1] >> 16; }\n";
       else
-        o << "  { const u32 t = reinterpret_cast<const PU32 *>(reinterpret_cast<const u8 *>(a.vals[" << d << "]) + i0)->v; r.v[" << d
-          << "][0] = t & 0xFFu; r.v[" << d << "][1] = (t >> 8) & 0xFFu; r.v[" << d << "][2] = (t >> 16) & 0xFFu; r.v[" << d << "][3] = t >> 24; }\n";
+        o << "  { const u32 t = reinterpret_cast<const PU32 *>(reinterpret_cast<const u8 *>(a.vals[" << d << "]) + i0)->v; r.v[" << v
+          << "][0] = t & 0xFFu; r.v[" << v << "][1] = (t >> 8) & 0xFFu; r.v[" << v << "][2] = (t >> 16) & 0xFFu; r.v[" << v << "][3] = t >> 24; }\n";
       o << "  r.ok[" << d << "] = reinterpret_cast<const PU32 *>(a.nulls[" << d << "] + i0)->v;\n";
     }
   } else {
@@ -1091,9 +1116,13 @@ std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, c
       snprintf(buf, sizeof(buf), elem, d);
       o << "  r.ok[" << d << "] = 0u;\n"
            "  for (int j = 0; j < 4; j++) {\n"
-           "    const bool in = (int)(i0 + j) < a.length;\n"
-           "    r.v[" << d << "][j] = in ? " << buf << " : 0u;\n"
-           "    r.ok[" << d << "] |= in ? (u32)a.nulls[" << d << "][i0 + j] << (8 * j) : 0u;\n"
+           "    const bool in = (int)(i0 + j) < a.length;\n";
+      if (width[d] > 4)  // (a wide slot's vector starts on a multiple of its width: word loads are aligned)
+        for (int k = 0; k < width[d] / 4; k++)
+          o << "    r.v[" << wb[d] + k << "][j] = in ? a.vals[" << d << "][" << width[d] / 4 << "ull * (i0 + j) + " << k << "] : 0u;\n";
+      else
+        o << "    r.v[" << wb[d] << "][j] = in ? " << buf << " : 0u;\n";
+      o << "    r.ok[" << d << "] |= in ? (u32)a.nulls[" << d << "][i0 + j] << (8 * j) : 0u;\n"
            "  }\n";
     }
   } else {
@@ -1125,7 +1154,7 @@ std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, c
       SL.valueBytes += width[d];
     }
     o << "    u64 h64;\n";
-    gen_row_hash64(o, SL, [](int d) { return "r.v[" + std::to_string(d) + "][j]"; },
+    gen_row_hash64(o, SL, [&](int d, int k) { return "r.v[" + std::to_string(wb[d] + k) + "][j]"; },
                    [](int d) { return "((r.ok[" + std::to_string(d) + "] >> (8 * j)) & 0xFFu)"; }, "h64", "    ");
     o << "    hh[j] = (u32)(h64 >> 32);\n"
          "    cv[j] = r.m[j];\n"

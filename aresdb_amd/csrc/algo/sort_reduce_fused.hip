@@ -1153,7 +1153,9 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
 //   sr_prefix_kernel   groups before each partition;
 //   sr_emit_kernel     <WIDE>: the representatives' dimension rows copied from `in` (ascending: the previous result's rows come
 //                      out in the order they lie in).
-// 4-byte dimensions (up to eight) and 4-byte integer aggregates; returns like fused_sort_reduce_run.
+// Up to eight dimensions in slots of 16 / 8 / 4 / 2 / 1 bytes (sort_vector_layout_supported: the scan is the one kernel that
+// reads the rows by slot width — the split and the merge see 64-bit hashes, the emit copies rows with copy_dim_row) and
+// integer aggregates of 4 or 8 bytes; returns like fused_sort_reduce_run.
 static int sort_reduce_vectors_run(int device, int length, const DimensionVector &in, const uint8_t *inValues, const DimensionVector &out,
                                    uint8_t *outValues, const AggSpec &a, hipStream_t stream, int slack, bool spread) {
   static const bool trace = getenv("ARES_HR_TRACE") != nullptr;  // diagnostics
@@ -1164,7 +1166,7 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
   if (!fused_sort_reduce_enabled() || !fused_sort_reduce_supported(a) || (a.width != 4 && a.width != 8) || length <= 0) return decline("aggregate");
   const DimLayoutD L = make_dim_layout(in.NumDimsPerDimWidth);
   const int nd = L.numDims;
-  if (nd < 1 || nd > kFusedDims || in.NumDimsPerDimWidth[0] || in.NumDimsPerDimWidth[1]) return decline("layout");  // (slots of 4 / 2 / 1 bytes)
+  if (!sort_vector_layout_supported(in.NumDimsPerDimWidth)) return decline("layout");  // (what the generated scan reads)
   int widths[kFusedDims];
   for (int d = 0; d < nd; d++) widths[d] = L.width[d];
   using T = Table<4, true>;  // (the 8-byte tables have the same number of slots)

@@ -27,8 +27,8 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
                           const DimensionVector &in, const uint8_t *inValues, int prevSize, const DimensionVector &out,
                           uint8_t *outValues, const AggSpec &a, hipStream_t stream);
 
-// The same over MATERIALISED vectors: rows [0, length) of `in` / `inValues` exist (4-byte dimensions, a 4-byte integer
-// aggregate); rows a previous fused Reduce left there are recognised by the row hashes kept beside them.  Returns alike.
+// The same over MATERIALISED vectors: rows [0, length) of `in` / `inValues` exist (a layout sort_vector_layout_supported
+// admits — slots of 16 / 8 / 4 / 2 / 1 bytes —, an integer aggregate of 4 or 8 bytes); rows a previous fused Reduce left there are recognised by the row hashes kept beside them.  Returns alike.
 int fused_sort_reduce_vectors(int device, int length, const DimensionVector &in, const uint8_t *inValues, const DimensionVector &out,
                               uint8_t *outValues, const AggSpec &a, hipStream_t stream);
 

@@ -2421,11 +2421,8 @@ bool vector_sort_enabled() {
   static EnvSwitch<bool> on("ARES_SORT_VECTORS", [](const char *e) { return !(e && e[0] == '0'); });
   return on.get();
 }
-bool vector_sort_layout(const DimensionVector &keys) {
-  int nd = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) nd += keys.NumDimsPerDimWidth[w];
-  return nd >= 1 && nd <= kFusedDims && !keys.NumDimsPerDimWidth[0] && !keys.NumDimsPerDimWidth[1];  // slots of 4 / 2 / 1 bytes
-}
+// (the predicate fused_sort_reduce_vectors declines by: Sort is never defined for a layout Reduce would turn away)
+bool vector_sort_layout(const DimensionVector &keys) { return sort_vector_layout_supported(keys.NumDimsPerDimWidth); }
 }  // namespace
 
 bool lazy_vector_sort_candidate(int device, const DimensionVector &keys, int length) {

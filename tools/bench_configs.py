@@ -256,6 +256,111 @@ def trips_leg(be, dev, rows, batch_rows=1 << 26, steps=3):
     return out
 
 
+def wide_key_legs(be, dev, which, rows, batch_rows=1 << 26, steps=3):
+    """Sort + Reduce over group keys in dimension slots of 8 and 16 bytes (rows of such a query exist when Sort arrives: a
+    transform into a wide slot runs at once), through the C++ driver in the Go call order, COUNT(*):
+      c3int64  C3's query with d2 stored as an Int64 dimension;
+      uuid     a UUID key of ~2 M distinct values and a Uint32 dimension of two, no filter.
+    Every key's count is compared with a torch bincount of the same rows, and the fetched rows must come in ascending order
+    of their 64-bit row hash.  ARES_SORT_VECTORS=0 in the environment gives the same legs on the real row sort."""
+    from aresdb_amd import check
+    from aresdb_amd.executor import Const
+    gen = torch.Generator(device=dev); gen.manual_seed(21)
+    nb = (rows + batch_rows - 1) // batch_rows
+    if which == "c3int64":
+        shard = workload.c3_shard(rows, batch_rows, seed=1, device=dev)
+        plan = queries.c3_plan(sort_measure="count")
+        plan.dimensions[2] = DimensionSpec(Col("d2"), abi.Int64)
+        names = ["ts", "d1", "d2", "d3"]
+        space = 169 * 101 * 51 * 3
+        want = torch.zeros(space, dtype=torch.int64, device=dev)
+        batches = []
+        for b in shard:
+            v = {k: b[k].values().to(torch.int64) for k in names}
+            ok = {k: b[k].valid() for k in names}
+            code = lambda k, x: torch.where(ok[k], x + 1, torch.zeros((), dtype=torch.int64, device=dev))
+            c = ((code("ts", v["ts"] // 3600) * 101 + code("d1", v["d1"])) * 51 + code("d2", v["d2"])) * 3 + code("d3", v["d3"])
+            want += torch.bincount(c[ok["d1"] & (v["d1"] < 90)], minlength=space)
+            cols = {k: b[k] for k in ("ts", "d1", "d3")}
+            cols["d2"] = workload._pack_column(v["d2"], ok["d2"], abi.Int64)  # the same values in an 8-byte column
+            batches.append(cols)
+            del v, ok, c
+        bytes_per_row = 4 + 4 + 8 + 4 + 4 / 8
+    else:
+        nkeys = 2_000_000
+        keys = torch.randint(-(1 << 62), 1 << 62, (nkeys, 2), dtype=torch.int64, device=dev, generator=gen)
+        names = ["key", "d3"]
+        plan = QueryPlan(filters=[], dimensions=[DimensionSpec(Col("key"), abi.UUID), DimensionSpec(Col("d3"), abi.Uint32)], measure=Const(1),
+                         agg=abi.AGGR_SUM_UNSIGNED, measure_type=abi.Uint32, use_hash_reduction=False)
+        want = torch.zeros(3 * nkeys, dtype=torch.int64, device=dev)
+        batches = []
+        for b in range(nb):
+            n = min(batch_rows, rows - b * batch_rows)
+            pick = torch.randint(0, nkeys, (n,), device=dev, generator=gen)
+            d3 = torch.randint(0, 2, (n,), dtype=torch.int32, device=dev, generator=gen)
+            ok3 = torch.rand((n,), device=dev, generator=gen) >= 0.01
+            d3 = torch.where(ok3, d3, torch.zeros((), dtype=torch.int32, device=dev))
+            want += torch.bincount(pick * 3 + torch.where(ok3, d3.to(torch.int64) + 1, torch.zeros((), dtype=torch.int64, device=dev)),
+                                   minlength=3 * nkeys)
+            kc = workload._pack_column(torch.stack([keys[:, 0][pick], keys[:, 1][pick]], dim=1).reshape(-1), None, abi.UUID)
+            kc.length = n  # (two int64 per value)
+            batches.append({"key": kc, "d3": workload._pack_column(d3, ok3, abi.Uint32)})
+            del pick, d3, ok3
+        bytes_per_row = 16 + 4 + 1 / 8
+    vps = [({k: rc.vp for k, rc in b.items()}, b[names[-1]].length) for b in batches]
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    packed = None
+    def run():
+        nonlocal packed
+        q = NativeQuery(be, plan, names, streams=streams)
+        if packed is None:
+            packed = q.pack_batches(vps)
+        q.run_batches(packed)
+        return q
+    compiles = -1
+    for _ in range(4):  # priming passes: the shape's scan is compiled in the background — until a pass builds nothing new
+        run().release()
+        state = be.rtc_wait()
+        if state is None or state["compiles"] == compiles:
+            break
+        compiles = state["compiles"]
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(steps):
+        run().release()
+    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+    be.profiler_enable(True)
+    q = run(); torch.cuda.synchronize()
+    kernels = be.profiler_report(); be.profiler_enable(False)
+    groups = q.result_size
+    dims, valids, meas = q.fetch()
+    q.release()
+    counts = meas.view(np.uint32).astype(np.int64)
+    width_order = sorted(range(len(dims)), key=lambda i: -plan.dimensions[i].width)  # (stable: vector order)
+    hashes = check.row_hashes_of_fetched([dims[i] for i in width_order], [valids[i] for i in width_order])
+    ordered = bool((hashes[1:] > hashes[:-1]).all())
+    want = want.cpu().numpy()
+    if which == "c3int64":
+        code = lambda v, ok, dt_: np.where(ok != 0, v.view(dt_).astype(np.int64) + 1, 0)
+        got = np.where(valids[0] != 0, dims[0].view("<u4").astype(np.int64) // 3600 + 1, 0) * 101 + code(dims[1], valids[1], "<u4")
+        got = (got * 51 + code(dims[2], valids[2], "<i8")) * 3 + code(dims[3], valids[3], "<u4")
+    else:
+        hk = keys.cpu().numpy().view(np.uint64)
+        pair = np.dtype([("hi", np.uint64), ("lo", np.uint64)])
+        kp = np.empty(len(hk), pair); kp["hi"], kp["lo"] = hk[:, 1], hk[:, 0]
+        order = np.argsort(kp)
+        gk = dims[0].view(np.uint64).reshape(-1, 2)
+        gp = np.empty(len(gk), pair); gp["hi"], gp["lo"] = gk[:, 1], gk[:, 0]
+        at = np.minimum(np.searchsorted(kp[order], gp), len(hk) - 1)
+        found = kp[order][at] == gp
+        got = np.where(found, order[at].astype(np.int64) * 3 + np.where(valids[1] != 0, dims[1].view("<u4").astype(np.int64) + 1, 0), -1)
+    ok = bool(groups == int((want > 0).sum()) and (got >= 0).all() and len(np.unique(got)) == len(got) and np.array_equal(want[got], counts))
+    return [{"config": "wide-keys", "leg": which, "sort_vectors": os.environ.get("ARES_SORT_VECTORS", "1") != "0", "rows": rows, "batches": nb,
+             "batch_rows": batch_rows, "groups": groups, "key_level_check": "ok" if ok else "MISMATCH", "ascending_row_hashes": ordered,
+             "ms_per_step": dt * 1e3, "rows_per_s": rows / dt, "algorithmic_bytes_per_row": bytes_per_row,
+             "kernel_ms_per_step": sum(ms for c, ms in kernels.values()),
+             "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}]
+
+
 def hll(be, dev, rows, groups, users, batches=2):
     """countdistincthll(user) group by g: `batches` batches of `rows` rows through the C++ driver."""
     from aresdb_amd.executor import Unary
@@ -320,6 +425,8 @@ def main():
     if "c4" in which: res += c4(be, dev, 1 << 26, 200_000)
     if "c4spec" in which: res += c4_spec(be, dev, int(float(os.environ.get("C4_ROWS", "1e9"))), int(float(os.environ.get("C4_KEYS", "5e7"))))
     if "trips" in which: res += trips_leg(be, dev, int(float(os.environ.get("TRIPS_ROWS", "1e9"))))
+    for leg in ("c3int64", "uuid"):
+        if leg in which: res += wide_key_legs(be, dev, leg, int(float(os.environ.get("WIDE_ROWS", str(1 << 28)))))
     if "hll" in which:
         res += hll(be, dev, 1 << 25, 1000, 5_000_000) + hll(be, dev, 1 << 25, 4, 50_000_000)
     if "geo" in which: res += geo(be, dev, 1 << 24, 100, 20) + geo(be, dev, 1 << 22, 250, 400)

@@ -174,6 +174,17 @@ int main(int argc, char **argv) {
     const int narrow[4] = {4, 4, 2, 1};
     if (int rc = build(rtc_sort_vector_scan_source(4, narrow, 9), "_vsort_narrow", "vector sort scan, slots 4 4 2 1")) return rc;
   }
+  {  // ... with slots of 8 and 16 bytes (Int64 / Uint64 / GeoPoint, UUID): UUID + Uint32; two 8-byte + two 4-byte slots; the
+     // widest row the scan takes (32 value bytes); Int64 over one slot of every narrower width; a GeoPoint alone, one partition
+    const int uuid4[2] = {16, 4}, i8844[4] = {8, 8, 4, 4}, w32[4] = {16, 8, 4, 4}, i8421[4] = {8, 4, 2, 1}, geo[1] = {8};
+    if (int rc = build(rtc_sort_vector_scan_source(2, uuid4, 9), "_vsort_16_4", "vector sort scan, slots 16 4")) return rc;
+    if (int rc = build(rtc_sort_vector_scan_source(4, i8844, 9), "_vsort_8_8_4_4", "vector sort scan, slots 8 8 4 4")) return rc;
+    if (int rc = build(rtc_sort_vector_scan_source(4, w32, 9), "_vsort_16_8_4_4", "vector sort scan, slots 16 8 4 4")) return rc;
+    if (int rc = build(rtc_sort_vector_scan_source(4, i8421, 9), "_vsort_8_4_2_1", "vector sort scan, slots 8 4 2 1")) return rc;
+    if (int rc = build(rtc_sort_vector_scan_source(1, geo, 0), "_vsort_8", "vector sort scan, slot 8, one partition")) return rc;
+    const int w40[3] = {16, 16, 8};  // beyond 32 value bytes: declined (the real Sort + Reduce runs)
+    if (!rtc_sort_vector_scan_source(3, w40, 9).empty()) { puts("a 40-byte row must be declined"); return 23; }
+  }
   // the vector-sourced scan (HashReduce on materialised dimension / measure vectors)
   for (int vw = 4; vw <= 8; vw += 4)
     for (int nd = 1; nd <= 4; nd += 3) {
