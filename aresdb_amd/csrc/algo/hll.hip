@@ -5,6 +5,10 @@
 //   1. key = dim-row hash with its low 16 bits replaced by the register id; stable radix sort of
 //      the batch's entries (sort_reduce.hip's one-sweep sort, payload = entry position);
 //   2. runs of equal keys -> (key, first row, max value), appended behind the previous results;
+//      (1 + 2, large batches: pre-aggregation — a generated scan deals {key, row, value} records out to
+//      512 partitions by a scramble of the key, one workgroup per partition folds them in an LDS table
+//      (max value, min row), and the sort and the run reduce see the surviving entries, not the rows;
+//      the result is the same entries bit for bit);
 //   3. stable merge of previous and current entries by (key ascending, value descending): one
 //      merge-path partition per 2048-entry output tile, then every tile ranks its two input
 //      segments against each other in LDS;
@@ -16,11 +20,16 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <cstring>
 #include <string>
 
 #include "ares_extensions.h"
 #include "common.hpp"
 #include "dim_layout.hpp"
+#include "hash_reduce_lds.hpp"
+#include "hr_kernels.hpp"
+#include "hr_rtc.hpp"
 #include "lookback.hpp"
 #include "sort_reduce.hpp"
 
@@ -302,6 +311,248 @@ __global__ __launch_bounds__(kBlock) void hll_gather_dims_kernel(const uint8_t *
 }
 
 // ---------------------------------------------------------------------------------------------
+// steps 1 + 2 on large batches: pre-aggregation of (dimension row, register) pairs before the sort
+// ---------------------------------------------------------------------------------------------
+// A batch of n rows holds at most groups x 16384 distinct keys — orders of magnitude fewer than rows in the shapes
+// HyperLogLog exists for.  max (of the value) and min (of the row) per key do not depend on the order of the rows:
+//   hll_scan_rtc        (hr_rtc.hip, generated for the dimension layout) reads rows [P, P + n) by slot width, hashes them
+//                       like Sort does and writes {row, key >> 32, value, (u32)key} to the workgroup's private stream of the
+//                       partition that a scramble of the whole key selects;
+//   hll_dedup_kernel    one workgroup per partition folds its streams in an LDS table keyed by the 64-bit key; a table that
+//                       fills up is emitted and cleared ("round"), so a key may survive more than once — over all emitted
+//                       entries of a key the max of the values and the min of the rows are those over the key's rows;
+//   sort_given_keys + hll_reduce_sorted(minIndex) over the m survivors leave what the row sort + first-of-run leave.
+// Everything up to the read-back of {m, stream overflow, index vector is not the range} writes temporaries only: a decline
+// (return -1) leaves no trace and the caller sorts the rows.
+constexpr int kPreaggPartBits = 9, kPreaggParts = 1 << kPreaggPartBits;
+constexpr int kDedupThreads = 1024;
+constexpr int kDedupSlots = 8192;             // 16 bytes per slot: 128 KB of the 160 KB of LDS
+constexpr int kDedupChunk = kDedupThreads;      // records folded between two looks at the table's fill
+constexpr int kDedupMaxKeys = 5120;           // emit + clear once the table holds more: <= 6144 keys (75 %) at any time
+constexpr uint64_t kDedupEmpty = ~0ull;       // (bits 14 and 15 of a key are zero)
+
+struct DedupParams {
+  const uint4 *rec;        // [streams][kPreaggParts][cap]
+  const uint32_t *counts;  // [streams][kPreaggParts]
+  uint32_t cap;
+  int streams;
+  uint32_t maxKeys;
+  uint64_t *keysOut;  // [<= n]
+  uint32_t *rowsOut;
+  uint32_t *valuesOut;
+  uint32_t *outCount;
+  uint32_t outCap;  // (every emitted entry stands for at least one record of its round: never reached)
+};
+
+__global__ __launch_bounds__(kDedupThreads) void hll_dedup_kernel(DedupParams p) {
+  __shared__ uint64_t sKey[kDedupSlots];
+  __shared__ uint32_t sVal[kDedupSlots], sRow[kDedupSlots];
+  __shared__ uint32_t sEnd[hr::kMaxStreams];  // records of streams [0, g] of this partition
+  __shared__ uint32_t sKeys, sEmit, sBase;
+  const uint32_t tid = threadIdx.x, part = blockIdx.x;
+  for (uint32_t s = tid; s < kDedupSlots; s += kDedupThreads) {
+    sKey[s] = kDedupEmpty;
+    sVal[s] = 0u;
+    sRow[s] = 0xFFFFFFFFu;
+  }
+  if (tid == 0) {
+    uint32_t total = 0;
+    for (int g = 0; g < p.streams; g++) {
+      const uint32_t c = p.counts[static_cast<uint64_t>(g) * kPreaggParts + part];
+      total += c < p.cap ? c : p.cap;
+      sEnd[g] = total;
+    }
+    sKeys = 0u;
+    sEmit = 0u;
+  }
+  __syncthreads();
+  const uint32_t total = sEnd[p.streams - 1];
+  for (uint32_t base = 0; base < total; base += kDedupChunk) {
+    const bool last = base + kDedupChunk >= total;
+#pragma unroll
+    for (int k = 0; k < kDedupChunk / kDedupThreads; k++) {
+      const uint32_t f = base + k * kDedupThreads + tid;
+      if (f >= total) continue;
+      int lo = 0, hi = p.streams - 1;  // the stream that holds flat record f: first g with sEnd[g] > f
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sEnd[mid] > f) hi = mid; else lo = mid + 1;
+      }
+      const uint32_t within = f - (lo ? sEnd[lo - 1] : 0u);
+      const uint4 r = p.rec[(static_cast<uint64_t>(lo) * kPreaggParts + part) * p.cap + within];
+      if (r.x == 0xFFFFFFFFu) continue;  // padding of the stream's last line
+      const uint64_t key = (static_cast<uint64_t>(r.y) << 32) | r.w;
+      uint32_t slot = static_cast<uint32_t>((key * 0x9E3779B97F4A7C15ull) >> 51);  // 13 bits
+      for (;;) {
+        uint64_t seen = sKey[slot];
+        if (seen == kDedupEmpty) {
+          seen = atomicCAS(reinterpret_cast<unsigned long long *>(&sKey[slot]), static_cast<unsigned long long>(kDedupEmpty),
+                           static_cast<unsigned long long>(key));
+          if (seen == kDedupEmpty) {
+            atomicAdd(&sKeys, 1u);
+            seen = key;
+          }
+        }
+        if (seen == key) break;
+        slot = (slot + 1u) & (kDedupSlots - 1);
+      }
+      atomicMax(&sVal[slot], r.z);
+      atomicMin(&sRow[slot], r.x);
+    }
+    __syncthreads();
+    const uint32_t keys = sKeys;
+    __syncthreads();  // (every lane has read the fill before the next chunk adds to it: the branch below is uniform)
+    if (keys > p.maxKeys || (last && keys > 0u)) {  // emit the table densely, clear it
+      if (tid == 0) sBase = atomicAdd(p.outCount, keys);
+      __syncthreads();
+      const uint32_t outBase = sBase;
+      for (uint32_t s = tid; s < kDedupSlots; s += kDedupThreads) {
+        const uint64_t key = sKey[s];
+        const bool used = key != kDedupEmpty;
+        const uint64_t peers = __ballot(used);
+        uint32_t waveAt = 0;
+        if ((tid & 63u) == 0u && peers) waveAt = atomicAdd(&sEmit, static_cast<uint32_t>(__popcll(peers)));
+        waveAt = __shfl(waveAt, 0);
+        if (used && outBase + keys <= p.outCap) {
+          const uint32_t at = outBase + waveAt + static_cast<uint32_t>(__popcll(peers & ((1ull << (tid & 63u)) - 1)));
+          p.keysOut[at] = key;
+          p.rowsOut[at] = sRow[s];
+          p.valuesOut[at] = sVal[s];
+          sKey[s] = kDedupEmpty;
+          sVal[s] = 0u;
+          sRow[s] = 0xFFFFFFFFu;
+        }
+      }
+      __syncthreads();
+      if (tid == 0) {
+        sKeys = 0u;
+        sEmit = 0u;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// the batch's index vector is the range [P, P + n) (query/hll.cu:68-69): the scan reads the rows it names in place
+__global__ __launch_bounds__(kBlock) void hll_index_range_kernel(const uint32_t *index, uint32_t first, int n, uint32_t *flag) {
+  bool off = false;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * kBlock)
+    off = off || index[i] != first + static_cast<uint32_t>(i);
+  if (__ballot(off) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+
+// ARES_HLL_PREAGG: unset = on, with the memory below; 1 = on for every batch that qualifies; 0 = the row sort always
+int preagg_mode() {
+  static EnvSwitch<int> mode("ARES_HLL_PREAGG", [](const char *e) { return !e || !e[0] ? 2 : (e[0] == '0' ? 0 : 1); });
+  return mode.get();
+}
+int64_t preagg_min_rows() {  // fixed launch costs and one more read-back: small batches keep the row sort
+  static EnvSwitch<int64_t> rows("ARES_HLL_PREAGG_MIN_ROWS",
+                                 [](const char *e) { return e && e[0] ? static_cast<int64_t>(atoll(e)) : int64_t(1) << 20; });
+  return rows.get();
+}
+uint32_t preagg_table_keys() {  // (tests: a small value makes every partition emit its table many times)
+  static EnvSwitch<int> keys("ARES_HLL_PREAGG_TABLE_KEYS", [](const char *e) { return e && e[0] ? atoi(e) : kDedupMaxKeys; });
+  const int k = keys.get();
+  return static_cast<uint32_t>(k < 1 ? 1 : (k > kDedupMaxKeys ? kDedupMaxKeys : k));
+}
+// What the device's last attempts saw: a batch whose streams overflowed (a few hot keys) or whose entries were hardly fewer
+// than its rows paid for the scan and gained nothing — the next kPreaggBackoff batches sort their rows, then one probes again.
+constexpr int kPreaggBackoff = 15;
+constexpr double kPreaggMaxRatio = 0.75;  // survivors / rows beyond which the stage does not pay
+std::atomic<int> g_preaggSkip[16];
+std::atomic<uint32_t> g_preaggGen{0};  // AresReloadEnv forgets the memory along with the switches
+std::atomic<uint64_t> g_preaggStats[4];  // batches pre-aggregated, declined, rows, survivors (AresHllPreaggStats)
+
+// steps 1 + 2 by pre-aggregation: the runs, or -1 (declined; nothing the caller can see was written)
+int hll_preagg_batch(const DimensionVector &prev, const DimensionVector &cur, uint32_t *prevValues, const uint32_t *curValues, int P,
+                     int n, hipStream_t stream) {
+  const int mode = preagg_mode();
+  if (mode == 0 || n < preagg_min_rows() || !rtc_scan_available()) return -1;
+  if (!sort_vector_layout_supported(cur.NumDimsPerDimWidth)) return -1;
+  const size_t capacity = static_cast<size_t>(cur.VectorCapacity);
+  if (static_cast<size_t>(P) + static_cast<size_t>(n) > capacity) return -1;  // (the scan reads rows [P, P + n) in place)
+  const int device = current_device();
+  std::atomic<int> &skip = g_preaggSkip[device & 15];
+  const uint32_t gen = g_envGeneration.load(std::memory_order_acquire);
+  if (g_preaggGen.exchange(gen, std::memory_order_acq_rel) != gen)
+    for (std::atomic<int> &s : g_preaggSkip) s.store(0, std::memory_order_relaxed);
+  if (mode == 2 && skip.load(std::memory_order_relaxed) > 0) {
+    skip.fetch_sub(1, std::memory_order_relaxed);
+    return -1;
+  }
+  const DimLayoutD L = make_dim_layout(cur.NumDimsPerDimWidth);
+  int widths[kFusedDims];
+  for (int d = 0; d < L.numDims; d++) widths[d] = L.width[d];
+  const RtcKernel scan = rtc_hll_scan_lookup(device, L.numDims, widths, kPreaggPartBits);
+  if (!scan) return -1;  // (being compiled in the background)
+
+  const int streams = rtc_scan_grid(n);
+  const uint64_t mean = (static_cast<uint64_t>(n) / (static_cast<uint64_t>(kPreaggParts) * streams)) << record_stream_slack();
+  const uint32_t cap = static_cast<uint32_t>(((2 * mean + 64 + 7) / 8 * 8) | 8ull);  // whole lines of 8, like the other scans' streams
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t headBytes = 256, countBytes = up(sizeof(uint32_t) * static_cast<size_t>(kPreaggParts) * streams);
+  const size_t recBytes = up(sizeof(uint4) * static_cast<size_t>(cap) * kPreaggParts * streams);
+  const size_t keyBytes = up(sizeof(uint64_t) * static_cast<size_t>(n)), wordBytes = up(sizeof(uint32_t) * static_cast<size_t>(n));
+  StreamBuffer buf(headBytes + countBytes + recBytes + keyBytes + 3 * wordBytes, stream);
+  uint8_t *at = buf.as<uint8_t>();
+  auto take = [&](size_t bytes) {
+    uint8_t *p = at;
+    at += bytes;
+    return p;
+  };
+  uint32_t *flags = reinterpret_cast<uint32_t *>(take(headBytes));  // [0] survivors, [1] stream overflow, [2] index vector is not the range
+  uint32_t *counts = reinterpret_cast<uint32_t *>(take(countBytes));
+  uint4 *rec = reinterpret_cast<uint4 *>(take(recBytes));
+  uint64_t *keys = reinterpret_cast<uint64_t *>(take(keyBytes));
+  uint32_t *rows = reinterpret_cast<uint32_t *>(take(wordBytes));
+  uint32_t *values = reinterpret_cast<uint32_t *>(take(wordBytes));
+  uint32_t *positions = reinterpret_cast<uint32_t *>(take(wordBytes));
+  hip_check(hipMemsetAsync(flags, 0, headBytes + countBytes, stream), "hipMemsetAsync");
+
+  ARES_LAUNCH("hll_index_range_kernel", hll_index_range_kernel, capped_grid((static_cast<int64_t>(n) + kBlock - 1) / kBlock, 256 * 8),
+              kBlock, stream, cur.IndexVector, static_cast<uint32_t>(P), n, flags + 2);
+  hr::Workspace ws;
+  memset(&ws, 0, sizeof(ws));
+  ws.outCount = flags;
+  ws.countsB = counts;
+  ws.recB = reinterpret_cast<uint32_t *>(rec);
+  ws.capB = cap;
+  ws.streams = streams;
+  ws.partBits = kPreaggPartBits;
+  ws.lineRecords = 8;
+  ws.rowBase = static_cast<uint32_t>(P);
+  rtc_hll_scan_launch(scan, prev.DimValues, capacity, curValues, L.numDims, widths, static_cast<uint32_t>(P), n, ws, stream);
+  DedupParams dp;
+  dp.rec = rec;
+  dp.counts = counts;
+  dp.cap = cap;
+  dp.streams = streams;
+  dp.maxKeys = preagg_table_keys();
+  dp.keysOut = keys;
+  dp.rowsOut = rows;
+  dp.valuesOut = values;
+  dp.outCount = flags;
+  dp.outCap = static_cast<uint32_t>(n);
+  ARES_LAUNCH("hll_dedup_kernel", hll_dedup_kernel, kPreaggParts, kDedupThreads, stream, dp);
+  uint32_t back[3] = {0, 0, 0};
+  read_back_u32(flags, back, 3, stream);
+  const int m = static_cast<int>(back[0]);
+  const bool declined = back[1] || back[2] || m <= 0 || m > n;
+  if (mode == 2 && (declined || static_cast<double>(m) > kPreaggMaxRatio * n)) skip.store(kPreaggBackoff, std::memory_order_relaxed);
+  if (declined) {
+    g_preaggStats[1].fetch_add(1, std::memory_order_relaxed);
+    return -1;
+  }
+  g_preaggStats[0].fetch_add(1, std::memory_order_relaxed);
+  g_preaggStats[2].fetch_add(static_cast<uint64_t>(n), std::memory_order_relaxed);
+  g_preaggStats[3].fetch_add(static_cast<uint64_t>(m), std::memory_order_relaxed);
+  sort_given_keys(keys, positions, m, stream);
+  return hll_reduce_sorted(keys, positions, rows, values, prev.HashValues + P, prev.IndexVector + P, prevValues + P, m, stream, true);
+}
+
+// ---------------------------------------------------------------------------------------------
 // result buffers come from libmem.so: the host frees them with DeviceFree
 // ---------------------------------------------------------------------------------------------
 using DeviceMallocFn = CGoCallResHandle (*)(void **, size_t);
@@ -413,7 +664,8 @@ int hyperloglog(const DimensionVector &prev, const DimensionVector &cur, uint32_
   const int P = prevResultSize, n = curBatchSize;
 
   int runs = 0;
-  if (n > 0) {
+  if (n > 0) runs = hll_preagg_batch(prev, cur, prevValues, curValues, P, n, stream);
+  if (n > 0 && runs < 0) {
     StreamBuffer positions(sizeof(uint32_t) * static_cast<size_t>(n), stream);
     sort_rows(prev.DimValues, L, capacity, cur.IndexVector, curValues, cur.HashValues, positions.as<uint32_t>(), true,
               n, stream);
@@ -443,6 +695,11 @@ int hyperloglog(const DimensionVector &prev, const DimensionVector &cur, uint32_
 }  // namespace ares
 
 using namespace ares;
+
+extern "C" void AresHllPreaggStats(unsigned long long *counters) {
+  if (!counters) return;
+  for (int i = 0; i < 4; i++) counters[i] = g_preaggStats[i].load(std::memory_order_relaxed);
+}
 
 extern "C" CGoCallResHandle HyperLogLog(DimensionVector prevDimOut, DimensionVector curDimOut, uint32_t *prevValuesOut,
                                         uint32_t *curValuesOut, int prevResultSize, int curBatchSize, bool isLastBatch,

@@ -1046,8 +1046,12 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
 // A row's values live in 32-bit words of `Raw::v`: one word per slot of 4, 2 or 1 bytes, two per 8-byte slot (Int64, Uint64,
 // GeoPoint), four per 16-byte slot (UUID) — at most kSortVectorValueBytes per row (sort_vector_layout_supported), which is
 // what four rows per lane leave of 128 VGPRs.
-std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, const int *widths = nullptr) {
+// hll (sort64 only): HyperLogLog's pre-aggregation scan (hll.hip).  The 4-byte value is the row's hll value; the 64-bit key is
+// the row hash with its low 16 bits replaced by the value's register id (query/functor.hpp:1296-1305) and the partition the
+// top PB bits of a scramble of the WHOLE key: the <= 16384 registers of one dimension row share the key's upper 48 bits.
+std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, const int *widths = nullptr, bool hll = false) {
   if (nd < 1 || nd > (sort64 ? kFusedDims : kGenericFusedDims) || (vw != 4 && vw != 8) || (sort64 && vw != 4)) return "";
+  if (hll && (!sort64 || partBits < 1 || partBits > 9)) return "";
   int width[kFusedDims] = {4, 4, 4, 4, 4, 4, 4, 4}, wb[kFusedDims] = {0, 1, 2, 3, 4, 5, 6, 7};
   bool narrow = false, wide = false;
   int valueBytes = 0, nw = 0;
@@ -1156,6 +1160,7 @@ std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, c
     o << "    u64 h64;\n";
     gen_row_hash64(o, SL, [&](int d, int k) { return "r.v[" + std::to_string(wb[d] + k) + "][j]"; },
                    [](int d) { return "((r.ok[" + std::to_string(d) + "] >> (8 * j)) & 0xFFu)"; }, "h64", "    ");
+    if (hll) o << "    h64 = (h64 & 0xFFFFFFFFFFFF0000ull) | (u64)(r.m[j] & 0x3FFFu);\n";
     o << "    hh[j] = (u32)(h64 >> 32);\n"
          "    cv[j] = r.m[j];\n"
          "    cw[j] = (u32)h64;\n"
@@ -1183,7 +1188,9 @@ std::string generate_vector(int nd, int vw, int partBits, bool sort64 = false, c
   // hashes are not known is hashed again, rows in ascending hash order of which every tile falls into ONE such partition —
   // the LOW PB bits of the top-bits partition index (a.chunkTiles = 32 - total partition bits) XORed with a scramble of its
   // leading bits: the tiles one workgroup scans lie a multiple of a power of two apart, the plain low bits would repeat)
-  if (sort64)
+  if (hll)
+    kernel_body_lines16(o, "cw[j]", "hll_scan_rtc", "(((hh[j] ^ (cw[j] * 0x9E3779B1u)) * 0x85EBCA6Bu) >> (32 - PB))");
+  else if (sort64)
     kernel_body_lines16(o, "cw[j]", "sr_scan_rtc",
                         "(a.pad ? (((hh[j] >> a.chunkTiles) ^ ((((hh[j] >> a.chunkTiles) >> PB) * 0x9E3779B1u) >> 23)) & (NP - 1u)) "
                         ": (PB ? hh[j] >> (32 - (PB ? PB : 1)) : 0u))");
@@ -2384,6 +2391,30 @@ void rtc_sort_vector_scan_launch(const RtcKernel &kernel, const uint8_t *dimValu
   launch_scan(kernel, args, ws.streams, length, stream, "sr_vector_scan_rtc");
 }
 std::string rtc_sort_vector_scan_source(int nd, const int *widths, int partBits) { return generate_vector(nd, 4, partBits, true, widths); }
+
+RtcKernel rtc_hll_scan_lookup(int device, int nd, const int *widths, int partBits, bool wait) {
+  if (!rtc_api().ok) return nullptr;
+  return compiled_kernel(device, generate_vector(nd, 4, partBits, true, widths, true), "hll_scan_rtc", wait);
+}
+void rtc_hll_scan_launch(const RtcKernel &kernel, const uint8_t *dimValues, size_t capacity, const uint32_t *hllValues, int nd, const int *widths,
+                         uint32_t rowBase, int length, const hr::Workspace &ws, hipStream_t stream) {
+  FusedPlanD plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.numCols = nd + 1;
+  size_t valueBytes = 0, off = 0;
+  for (int d = 0; d < nd; d++) valueBytes += static_cast<size_t>(widths ? widths[d] : 4);
+  for (int d = 0; d < nd; d++) {
+    const size_t w = static_cast<size_t>(widths ? widths[d] : 4);
+    plan.cols[d].vals = reinterpret_cast<const uint32_t *>(dimValues + off * capacity + w * rowBase);
+    plan.cols[d].nulls = dimValues + valueBytes * capacity + static_cast<size_t>(d) * capacity + rowBase;
+    off += w;
+  }
+  plan.cols[nd].vals = hllValues;  // (entry i of the batch is dimension row rowBase + i)
+  RtcArgs args;
+  fill_scan_args(args, plan, rowBase, length, ws);
+  launch_scan(kernel, args, ws.streams, length, stream, "hll_scan_rtc");
+}
+std::string rtc_hll_scan_source(int nd, const int *widths, int partBits) { return generate_vector(nd, 4, partBits, true, widths, true); }
 
 RtcKernel rtc_vector_merge_lookup(int device, int nd, int vw, int partBits, const AggSpec &a, bool wait) {
   if (!rtc_api().ok) return nullptr;

@@ -57,6 +57,14 @@ void rtc_sort_vector_scan_launch(const RtcKernel &kernel, const uint8_t *dimValu
                                  const int *widths, uint32_t rowBase, int length, int totalPartBits, bool spread, const hr::Workspace &ws,
                                  hipStream_t stream);
 std::string rtc_sort_vector_scan_source(int nd, const int *widths, int partBits);
+// HyperLogLog's pre-aggregation scan (hll.hip) over entries [0, length) of a batch whose dimension rows are rows [rowBase,
+// rowBase + length) of a materialised dimension vector (same layouts) and whose 4-byte hll values are hllValues[0, length):
+// records {rowBase + entry, key >> 32, hll value, (u32)key} with key = (row hash & ~0xFFFF) | (value & 0x3FFF), in the stream of
+// the partition that the top partBits (1 .. 9) bits of a scramble of the whole key select.
+RtcKernel rtc_hll_scan_lookup(int device, int nd, const int *widths, int partBits, bool wait = false);
+void rtc_hll_scan_launch(const RtcKernel &kernel, const uint8_t *dimValues, size_t capacity, const uint32_t *hllValues, int nd, const int *widths,
+                         uint32_t rowBase, int length, const hr::Workspace &ws, hipStream_t stream);
+std::string rtc_hll_scan_source(int nd, const int *widths, int partBits);
 // TABLE-mode scan of `plan` (low cardinality): LDS aggregation per workgroup, one record per group into region A
 // (what hr::flush_table writes), rtc_scan_grid(length) workgroups; the generic merge reads it.
 RtcKernel rtc_table_scan_lookup(int device, const FusedPlanD &plan, int nd, int partBits, const AggSpec &a, const hr::Widen &w,

@@ -407,13 +407,34 @@ __global__ __launch_bounds__(kBlock) void sort_const_hash_kernel(uint64_t *hashe
     hashes[i] = h;
 }
 
+// the keys are there already (HyperLogLog's pre-aggregated entries): digit histograms, payload = entry positions
+__global__ __launch_bounds__(kBlock) void sort_key_hist_kernel(const uint64_t *keys, int n, uint32_t *globalHist /* [8][256] */,
+                                                               uint32_t *iotaOut) {
+  __shared__ uint32_t sHist[8 * 256];
+  for (int i = threadIdx.x; i < 8 * 256; i += kBlock) sHist[i] = 0;
+  __syncthreads();
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * kBlock) {
+    const uint64_t h = keys[i];
+    iotaOut[i] = static_cast<uint32_t>(i);
+#pragma unroll
+    for (int p = 0; p < 8; p++) atomicAdd(&sHist[p * 256 + ((h >> (8 * p)) & 255)], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 8 * 256; i += kBlock) {
+    const uint32_t c = sHist[i];
+    if (c) atomicAdd(&globalHist[i], c);
+  }
+}
+
 void sort_rows(const uint8_t *dimValues, const DimLayoutD &L, size_t capacity, const uint32_t *rowIndex,
                const uint32_t *hllValues, uint64_t *keyVector, uint32_t *payload, bool iotaPayload, int length,
                hipStream_t stream) {
   if (length <= 0) return;
   if (static_cast<int64_t>(length) >= (1ll << 30))
     throw std::invalid_argument("Sort supports up to 2^30 - 1 rows per call");
-  if (L.numDims == 0 && !hllValues) {  // a stable sort of equal keys leaves the index vector untouched
+  const bool givenKeys = !dimValues && !rowIndex;  // (sort_given_keys)
+  if (L.numDims == 0 && !hllValues && !givenKeys) {  // a stable sort of equal keys leaves the index vector untouched
     ARES_LAUNCH("sort_const_hash_kernel", sort_const_hash_kernel, capped_grid((static_cast<int64_t>(length) + kBlock - 1) / kBlock, 256 * 8),
                 kBlock, stream, keyVector, length);
     return;
@@ -428,7 +449,7 @@ void sort_rows(const uint8_t *dimValues, const DimLayoutD &L, size_t capacity, c
   // Row hashes are sorted by their top half and fixed up (above); HyperLogLog keys carry the register id in their low
   // 16 bits — equal top halves are the rule there — and keep the eight passes.  ARES_SORT_TOPBITS=0: eight passes always.
   static EnvSwitch<bool> topBits("ARES_SORT_TOPBITS", [](const char *e) { return !(e && e[0] == '0'); });
-  const bool topOnly = !hllValues && topBits.get();
+  const bool topOnly = !hllValues && !givenKeys && topBits.get();
   const int fixGrid = capped_grid((static_cast<int64_t>(length) + kBlock - 1) / kBlock, 256 * 16);
   const uint32_t capPerGroup = static_cast<uint32_t>(length / 8 / fixGrid + 64);  // (expected: length^2 / 2^33 / fixGrid each)
   const size_t workCap = topOnly ? static_cast<size_t>(capPerGroup) * fixGrid : 0;
@@ -451,8 +472,11 @@ void sort_rows(const uint8_t *dimValues, const DimLayoutD &L, size_t capacity, c
   hip_check(hipMemsetAsync(base, 0, offStatus, stream), "hipMemsetAsync");
 
   const int grid = capped_grid((static_cast<int64_t>(length) + kBlock - 1) / kBlock, 256 * 8);
-  ARES_LAUNCH("sort_hash_hist_kernel", sort_hash_hist_kernel, grid, kBlock, stream, dimValues, L, capacity, rowIndex,
-              keyVector, length, hist, hllValues, iotaPayload ? payload : nullptr);
+  if (givenKeys)
+    ARES_LAUNCH("sort_key_hist_kernel", sort_key_hist_kernel, grid, kBlock, stream, keyVector, length, hist, payload);
+  else
+    ARES_LAUNCH("sort_hash_hist_kernel", sort_hash_hist_kernel, grid, kBlock, stream, dimValues, L, capacity, rowIndex,
+                keyVector, length, hist, hllValues, iotaPayload ? payload : nullptr);
   ARES_LAUNCH("digit_start_kernel", digit_start_kernel, 8, 256, stream, hist);
   const int passGrid = capped_grid(numTiles, 256 * 3);
   auto run_passes = [&](int first) {  // an even number of passes: the data ends where it started (keyVector / payload)
@@ -494,6 +518,10 @@ void sort_rows(const uint8_t *dimValues, const DimLayoutD &L, size_t capacity, c
     read_back_u32(tickets + 8, &err, 1, stream);
     if (err) throw AlgorithmError("ERROR: Sort: inter-tile scan timed out");
   }
+}
+
+void sort_given_keys(uint64_t *keyVector, uint32_t *payload, int length, hipStream_t stream) {
+  sort_rows(nullptr, DimLayoutD{}, 0, nullptr, nullptr, keyVector, payload, true, length, stream);
 }
 
 static void sort_impl(const DimensionVector &keys, int length, hipStream_t stream) {
@@ -546,7 +574,10 @@ __global__ __launch_bounds__(kBlock) void fill_identity_kernel(uint8_t *values, 
     store_value_bits(values, a, static_cast<size_t>(i), a.identity);
 }
 
-template <bool HLL>
+// HLL: 0 = Reduce; 1 = HyperLogLog, a run's index is that of its first entry (rows were sorted stably); 2 = HyperLogLog over
+// pre-aggregated entries, which arrive in no particular row order: a run's index is the minimum of its entries' (indexOut
+// starts at ~0)
+template <int HLL>
 __global__ __launch_bounds__(kBlock) void reduce_kernel(ReduceParams p) {
   __shared__ uint32_t sTrailG[kWaves], sTrailWhole[kWaves];
   __shared__ uint64_t sTrailP[kWaves];
@@ -619,7 +650,10 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(ReduceParams p) {
         if (open) aggregate_slot(p.valuesOut + static_cast<size_t>(p.agg.width) * group,
                                  reinterpret_cast<const uint8_t *>(&acc), p.agg);
         group++;
-        if (HLL) {
+        if (HLL == 2) {
+          atomicMin(p.indexOut + group, p.indexSrc[idx[j]]);
+          p.hashOut[group] = h[j];
+        } else if (HLL) {
           p.indexOut[group] = p.indexSrc[idx[j]];
           p.hashOut[group] = h[j];
         } else {
@@ -630,6 +664,7 @@ __global__ __launch_bounds__(kBlock) void reduce_kernel(ReduceParams p) {
       } else {
         const uint64_t v = load_value_bits(p.valuesIn, p.agg, idx[j]);
         acc = open ? combine_bits(p.agg, acc, v) : v;
+        if (HLL == 2) atomicMin(p.indexOut + group, p.indexSrc[idx[j]]);
       }
       open = true;
     }
@@ -709,7 +744,7 @@ static int reduce_impl(const DimensionVector &in, uint8_t *inputValues, const Di
   ARES_LAUNCH("fill_identity_kernel", fill_identity_kernel, fillGrid, kBlock, stream, outputValues, p.agg, length);
   p.indexSrc = nullptr;
   p.hashOut = nullptr;
-  ARES_LAUNCH("reduce_kernel", reduce_kernel<false>, capped_grid(p.numTiles), kBlock, stream, p);
+  ARES_LAUNCH("reduce_kernel", reduce_kernel<0>, capped_grid(p.numTiles), kBlock, stream, p);
   uint32_t result[2] = {0, 0};  // {groups, error}
   read_back_u32(p.total, result, 2, stream);
   if (result[1]) throw AlgorithmError("ERROR: Reduce: inter-tile scan timed out");
@@ -729,7 +764,7 @@ int reduce_now(const DimensionVector &in, uint8_t *inputValues, const DimensionV
 
 int hll_reduce_sorted(const uint64_t *keys, const uint32_t *positions, const uint32_t *indexSrc,
                       const uint32_t *valuesSrc, uint64_t *hashOut, uint32_t *indexOut, uint32_t *valuesOut,
-                      int length, hipStream_t stream) {
+                      int length, hipStream_t stream, bool minIndex) {
   if (length <= 0) return 0;
   ReduceParams p;
   p.agg = make_agg_spec(AGGR_MAX_UNSIGNED, 4);
@@ -754,7 +789,12 @@ int hll_reduce_sorted(const uint64_t *keys, const uint32_t *positions, const uin
   p.error = ws.as<uint32_t>() + 2;
   p.status = reinterpret_cast<uint64_t *>(ws.as<uint8_t>() + 16);
   hip_check(hipMemsetAsync(valuesOut, 0, sizeof(uint32_t) * static_cast<size_t>(length), stream), "hipMemsetAsync");
-  ARES_LAUNCH("hll_reduce_kernel", reduce_kernel<true>, capped_grid(p.numTiles), kBlock, stream, p);
+  if (minIndex) {
+    hip_check(hipMemsetAsync(indexOut, 0xFF, sizeof(uint32_t) * static_cast<size_t>(length), stream), "hipMemsetAsync");
+    ARES_LAUNCH("hll_reduce_kernel", reduce_kernel<2>, capped_grid(p.numTiles), kBlock, stream, p);
+  } else {
+    ARES_LAUNCH("hll_reduce_kernel", reduce_kernel<1>, capped_grid(p.numTiles), kBlock, stream, p);
+  }
   uint32_t result[2] = {0, 0};  // {runs, error}
   read_back_u32(p.total, result, 2, stream);
   if (result[1]) throw AlgorithmError("ERROR: HyperLogLog: inter-tile scan timed out");

@@ -134,6 +134,16 @@ size_t AresStreamEvents(int device, void *stream);
  * pile up batch after batch).  Either pointer may be NULL. */
 void AresTempStats(size_t *handedOutBytes, size_t *cachedBytes);
 
+/* HyperLogLog folds a large batch's (dimension row, register) pairs in LDS before it sorts: the radix sort and the run
+ * reduce then see the entries that survive, not the rows (algo/hll.hip; the result is the same bit for bit).  Switches, all
+ * obeying AresReloadEnv: ARES_HLL_PREAGG=0 sorts rows always, =1 pre-aggregates every batch that qualifies, unset does so
+ * too but lets a device sort rows for 15 batches after one whose record streams overflowed (a few hot keys) or whose
+ * survivors exceeded 3/4 of its rows; ARES_HLL_PREAGG_MIN_ROWS (default 1048576) is the smallest batch that takes the
+ * stage; ARES_HLL_PREAGG_TABLE_KEYS (tests; <= 5120) is the number of keys after which a partition's table is emitted.
+ * counters receives {batches pre-aggregated, batches that declined after the scan, rows of the former, their surviving
+ * entries} since the process started. */
+void AresHllPreaggStats(unsigned long long *counters);
+
 /* Fused batch execution: filter -> dimension / measure projection -> hash reduction of ONE batch in
  * a single pass over the source columns, without the index / predicate / dimension vectors the
  * one-call-per-AST-node ABI materialises in between (~145 B/row of HBM traffic on

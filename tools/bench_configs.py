@@ -372,17 +372,34 @@ def hll(be, dev, rows, groups, users, batches=2):
         gcol = torch.randint(0, groups, (rows,), dtype=torch.int32, device=dev, generator=gen)
         ucol = torch.randint(0, users, (rows,), dtype=torch.int32, device=dev, generator=gen)
         cols.append((workload._pack_column(gcol, None, abi.Uint32), workload._pack_column(ucol, None, abi.Uint32)))
+    import ctypes
+    def preagg():  # {batches pre-aggregated, declined after the scan, their rows, the surviving entries} (ARES_HLL_PREAGG=0: all zero)
+        c = (ctypes.c_ulonglong * 4)()
+        be._algo.AresHllPreaggStats.argtypes, be._algo.AresHllPreaggStats.restype = [ctypes.POINTER(ctypes.c_ulonglong)], None
+        be._algo.AresHllPreaggStats(c)
+        return [int(x) for x in c]
     def run():
         q = NativeQuery(be, plan, ["g", "user"])
+        before, ratios, start = preagg(), [], preagg()
         for b, (cg, cu) in enumerate(cols):
             q.run({"g": cg.vp, "user": cu.vp}, rows, is_last_batch=b == batches - 1)
+            now = preagg()
+            ratios.append(round((now[3] - before[3]) / (now[2] - before[2]), 4) if now[2] > before[2] else None)  # m / n; None: rows were sorted
+            before = now
         n = q.result_size
         dims, valids, counts, vec = q.fetch_hll()
-        q.release(); return n, int(counts.astype(np.int64).sum()), len(vec)
-    dt, k, (n, regs, nbytes) = timed(be, run)
-    return [{"config": "HLL", "rows": rows * batches, "groups": groups, "users": users, "result_dims": n, "registers": regs,
-             "hll_bytes": nbytes, "ms": dt * 1e3, "rows_per_s": rows * batches / dt,
-             "kernels": {n_: round(ms / c, 4) for n_, (c, ms) in k.items()}}]
+        end = preagg()
+        q.release(); return n, int(counts.astype(np.int64).sum()), len(vec), (ratios, end[0] - start[0], end[1] - start[1])
+    run(); be.rtc_wait()  # (the scan generated for the layout is compiled in the background: the timed runs find it loaded)
+    dt, k, (n, regs, nbytes, (ratios, took, declined)) = timed(be, run)
+    total = sum(ms for c, ms in k.values())
+    front = ("hll_scan_rtc", "hll_dedup_kernel", "hll_index_range_kernel", "sort_key_hist_kernel", "sort_hash_hist_kernel", "digit_start_kernel",
+             "radix_pass_kernel", "hll_reduce_kernel")  # steps 1 + 2; everything else is the merge, the encoding and the transforms
+    return [{"config": "HLL", "rows": rows * batches, "batches": batches, "groups": groups, "users": users, "result_dims": n, "registers": regs,
+             "hll_bytes": nbytes, "ms": dt * 1e3, "rows_per_s": rows * batches / dt, "survivors_per_row": ratios, "batches_preaggregated": took, "batches_declined": declined,
+             "kernel_ms": round(total, 3), "sort_reduce_share": round(sum(ms for n_, (c, ms) in k.items() if n_ in front) / total, 3) if total else None,
+             "kernels": {n_: round(ms / c, 4) for n_, (c, ms) in k.items()},
+             "kernel_total_ms": {n_: round(ms, 3) for n_, (c, ms) in sorted(k.items(), key=lambda kv: -kv[1][1])}}]
 
 
 def geo(be, dev, rows, num_shapes, pts_per_shape):
@@ -428,7 +445,7 @@ def main():
     for leg in ("c3int64", "uuid"):
         if leg in which: res += wide_key_legs(be, dev, leg, int(float(os.environ.get("WIDE_ROWS", str(1 << 28)))))
     if "hll" in which:
-        res += hll(be, dev, 1 << 25, 1000, 5_000_000) + hll(be, dev, 1 << 25, 4, 50_000_000)
+        res += hll(be, dev, 1 << 25, 1000, 5_000_000) + hll(be, dev, 1 << 25, 4, 50_000_000) + hll(be, dev, 1 << 25, 100, 50_000_000, batches=4)
     if "geo" in which: res += geo(be, dev, 1 << 24, 100, 20) + geo(be, dev, 1 << 22, 250, 400)
     for r in res: print(json.dumps(r), flush=True)
     os.makedirs("gpurun_out", exist_ok=True)

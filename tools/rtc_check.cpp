@@ -185,6 +185,16 @@ int main(int argc, char **argv) {
     const int w40[3] = {16, 16, 8};  // beyond 32 value bytes: declined (the real Sort + Reduce runs)
     if (!rtc_sort_vector_scan_source(3, w40, 9).empty()) { puts("a 40-byte row must be declined"); return 23; }
   }
+  {  // HyperLogLog's pre-aggregation scan (hll.hip): the same rows, keyed by (row hash & ~0xFFFF) | register id, 512 partitions
+     // chosen by a scramble of the whole key — one dimension, four narrow ones, eight, a UUID + Uint32, the widest row
+    const int one[1] = {4}, narrow[4] = {4, 4, 2, 1}, uuid4[2] = {16, 4}, w32[4] = {16, 8, 4, 4};
+    if (int rc = build(rtc_hll_scan_source(1, one, 9), "_hll1", "hll scan, slot 4")) return rc;
+    if (int rc = build(rtc_hll_scan_source(4, narrow, 9), "_hll_narrow", "hll scan, slots 4 4 2 1")) return rc;
+    if (int rc = build(rtc_hll_scan_source(8, nullptr, 9), "_hll8", "hll scan nd 8")) return rc;
+    if (int rc = build(rtc_hll_scan_source(2, uuid4, 9), "_hll_16_4", "hll scan, slots 16 4")) return rc;
+    if (int rc = build(rtc_hll_scan_source(4, w32, 9), "_hll_16_8_4_4", "hll scan, slots 16 8 4 4")) return rc;
+    if (!rtc_hll_scan_source(1, one, 0).empty()) { puts("an hll scan without partitions must be declined"); return 24; }
+  }
   // the vector-sourced scan (HashReduce on materialised dimension / measure vectors)
   for (int vw = 4; vw <= 8; vw += 4)
     for (int nd = 1; nd <= 4; nd += 3) {
