@@ -9,14 +9,18 @@ One "step" = one full pass of the query over the rank's shard (all batches, redu
 N > 1 also the cross-device merge of the per-shard group tables).  N ranks = N shards (weak
 scaling): `value` = rows of all shards / max-over-ranks step time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch-rows B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--batch-rows B] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no torchrun environment spawns the N ranks itself (one process per GPU).
-Outside the timed region the final group table is verified key by key (aresdb_amd/check.py), the
-reference's own HOST build is timed on a bounded sample (cpu_baseline) and compared key by key with
-the same independent group-by, and a few secondary legs are reported (never `value`): the same query
-with the in-ABI fusion stages switched off, at the reference's live-batch size, and through the
-explicit fused extension.  `--dump-outputs DIR` writes the group table the last timed step returned to
+A plain run does what `value` needs and nothing else: it generates the shard, primes the shape's
+kernels, warms up, times the K steps and prints the result line.  `--full` adds, outside the timed
+region, everything else this file measures or checks: the final group table is verified key by key
+(aresdb_amd/check.py), every kernel is timed in a profiled pass of its own and its HBM traffic counted
+(roofline), the reference's own HOST build is timed on a bounded sample (cpu_baseline) and compared key
+by key with the same independent group-by, and the secondary legs are reported (never `value`): a fresh
+process's first query, the same query with the in-ABI fusion stages switched off, at the reference's
+live-batch size, through the explicit fused extension, and so on.  The keys those fill are null in a
+plain run's line.  `--dump-outputs DIR` writes the group table the last timed step returned to
 DIR/<name>.npy (dump_outputs): the shard is generated from a fixed seed, so two builds run with the same
 arguments can be compared array by array.
 """
@@ -483,6 +487,11 @@ def main(argv=None, backend=None, tensor_device=None):
     ap.add_argument("--rows", type=float, default=1e9, help="rows per GPU (shard size)")
     ap.add_argument("--batch-rows", type=float, default=float(1 << 26))
     ap.add_argument("--null-fraction", type=float, default=0.01)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, outside the timed region: the key-level check of the final group table, the "
+                         "profiled pass and the traffic counters behind `roofline`, the reference's CPU baseline and the secondary "
+                         "legs (--no-cpu-baseline, --no-legs / --legs / --leg-budget and --no-pmc trim them); off: a plain run, "
+                         "whose line leaves those keys null")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (fusion off, live batches, extension)")
     ap.add_argument("--legs", default="all", help="comma list of substrings: only the secondary legs whose name contains one of them")
@@ -518,6 +527,8 @@ def main(argv=None, backend=None, tensor_device=None):
     ap.add_argument("--leg", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--fused-extension", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.leg:
+        args.full = True  # a leg is one configuration measured in full: its steps, its kernels, its check
 
     if args.single_process:
         return single_process(args, backend, tensor_device)
@@ -526,7 +537,7 @@ def main(argv=None, backend=None, tensor_device=None):
     # DIRECT-mode workspace was sized for a region it does not write, 4.3 GB of fresh device memory in a query's second
     # or third batch — profiles/r4_experiments.md "cold start".)
     early_legs = {}
-    if backend is None and args.gpus <= 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not (args.leg or args.cold or args.no_legs) and \
+    if args.full and backend is None and args.gpus <= 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not (args.leg or args.cold or args.no_legs) and \
             (args.legs == "all" or any("cold" in w for w in args.legs.split(","))):
         import tempfile
         cold_argv = ["--rows", str(int(args.rows)), "--null-fraction", str(args.null_fraction), "--steps", "3", "--warmup", "1",
@@ -739,11 +750,11 @@ def main(argv=None, backend=None, tensor_device=None):
     drv1 = be.mem_driver_calls(device_index)
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, last.fetch(), measure_dtype)
-    # ---- per-kernel durations: the same steps once more with HIP events around every launch (on the launch's own
-    # stream, inside the library) — outside the timed region, so that the events cost `value` nothing; the pass's
+    # ---- --full, per-kernel durations: the same steps once more with HIP events around every launch (on the launch's
+    # own stream, inside the library) — outside the timed region, so that the events cost `value` nothing; the pass's
     # own wall time is reported next to ms_per_step
     kernels, profiled_ms, prof_steps = {}, None, 0
-    if be.has_profiler:
+    if args.full and be.has_profiler:
         prof_steps = max(1, min(args.steps, 5))
         sync()
         be.profiler_enable(True)
@@ -765,7 +776,7 @@ def main(argv=None, backend=None, tensor_device=None):
         elapsed = max(float(g[0]) for g in gathered)
     ctx = last
 
-    # ---- outside the timed region: key-level verification of this rank's final group table ----
+    # ---- outside the timed region: the size of this rank's final group table; --full: its key-level verification ----
     merged_groups = merged_check = None
     if distributed:  # `ctx` holds the merged table of all shards: check it, then redo the shard alone
         merged_groups = int(merged)
@@ -776,9 +787,9 @@ def main(argv=None, backend=None, tensor_device=None):
             merged_check = compare_fetched(ctx.fetch(), expected_groups(every))
         ctx.release()
         ctx = run_shard(be, plan, vps, device_index, streams)
-    report = compare_fetched(ctx.fetch(), expected_groups(batches))
+    report = compare_fetched(ctx.fetch(), expected_groups(batches)) if args.full else None
     groups = ctx.result_size
-    ok = report["status"] == "ok" and report["groups"] == groups
+    ok = report is None or (report["status"] == "ok" and report["groups"] == groups)
     if merged_check is not None:
         ok = ok and merged_check["status"] == "ok" and merged_check["groups"] == merged_groups
     ctx.release()
@@ -799,11 +810,11 @@ def main(argv=None, backend=None, tensor_device=None):
     # HBM bytes per launch: measured now by two rocprofv3 --pmc passes (rank 0 of a 1-GPU run), else — same build of
     # libalgorithm.so and same batch size only — from the committed passes under profiles/, else null
     pmc_kernels, pmc_note = {}, "not measured (--no-pmc)"
-    if rank == 0 and world == 1 and on_gpu and not args.no_pmc and not args.leg:
+    if args.full and rank == 0 and world == 1 and on_gpu and not args.no_pmc and not args.leg:
         t_pmc0 = time.perf_counter()
         pmc_kernels, pmc_note = measure_traffic(batch_rows)
         pmc_note += f" ({time.perf_counter() - t_pmc0:.0f} s)"
-    if not pmc_kernels:
+    if args.full and not pmc_kernels:
         try:
             pmc = json.load(open(os.path.join(ROOT, "profiles", "r6_c3_pmc_traffic.json")))
             if pmc.get("rows_per_batch") == batch_rows and pmc.get("libalgorithm_sha256_16") == library_sha() and on_gpu:
@@ -832,7 +843,7 @@ def main(argv=None, backend=None, tensor_device=None):
 
     cpu = ref_check = None
     legs = {}
-    if rank == 0 and world == 1 and on_gpu:
+    if args.full and rank == 0 and world == 1 and on_gpu:
         if not args.no_cpu_baseline:
             cpu, ref_fetched, ref_slices = cpu_baseline(batches, c3_plan, args.cpu_budget)
             if cpu is not None:  # the reference's HOST result of the sample, key by key against the same group-by
@@ -964,7 +975,7 @@ def main(argv=None, backend=None, tensor_device=None):
         c4 = legs.get("c4_spec_1B_rows_50M_keys")
         tr = legs.get("trips_shaped_1B_rows_u16_dim_u8_filter")
         out["summary"] = {
-            "value_rows_per_s": value, "ms_per_step": out["ms_per_step"], "check_groups": report["status"],
+            "value_rows_per_s": value, "ms_per_step": out["ms_per_step"], "check_groups": report and report["status"],
             "roofline_frac_dominant_kernel": None if roofline is None else round(roofline["frac"], 4),
             "dominant_kernel": None if roofline is None else roofline["kernel"],
             "traffic_over_algorithmic": None if roofline is None else roofline.get("traffic_over_algorithmic"),
@@ -998,7 +1009,7 @@ def main(argv=None, backend=None, tensor_device=None):
         be.call("DestroyCudaStream", s, device_index)
     if not ok:
         if rank == 0:
-            print(f"bench.py: verification failed: {report['status']} / {ref_check}", file=sys.stderr)
+            print(f"bench.py: verification failed: {report and report['status']} / {merged_check and merged_check['status']} / {ref_check}", file=sys.stderr)
         sys.exit(1)
     return 0
 

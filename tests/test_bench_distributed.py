@@ -35,7 +35,7 @@ def test_two_rank_path_merges_and_verifies(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29533", os.path.join(H.ROOT, "tests", "bench_dist_harness.py"), "--gpus", "2", "--rows", "6000",
-           "--batch-rows", "2500", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-legs", "--verify-merged",
+           "--batch-rows", "2500", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-legs", "--verify-merged",
            "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, cwd=H.ROOT, env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -56,7 +56,7 @@ def test_eight_rank_path_merges_and_verifies():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8", "--master-addr", "127.0.0.1",
            "--master-port", "29541", os.path.join(H.ROOT, "tests", "bench_dist_harness.py"), "--gpus", "8", "--rows", "5000",
-           "--batch-rows", "2500", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-legs", "--verify-merged"]
+           "--batch-rows", "2500", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-legs", "--verify-merged"]
     r = subprocess.run(cmd, cwd=H.ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])

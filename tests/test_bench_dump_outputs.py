@@ -25,7 +25,8 @@ def _load(directory):
 
 def test_dump_is_the_last_steps_table_and_repeats(tmp_path, capsys, monkeypatch):
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))  # (bench_full.json lands there)
-    argv = ["--gpus", "1", "--rows", "6000", "--batch-rows", "2500", "--steps", "2", "--warmup", "0", "--no-cpu-baseline", "--no-legs"]
+    argv = ["--gpus", "1", "--rows", "6000", "--batch-rows", "2500", "--steps", "2", "--warmup", "0", "--full", "--no-cpu-baseline",
+            "--no-legs"]
     for d in ("a", "b"):
         assert bench.main(argv + ["--dump-outputs", str(tmp_path / d)], backend=H.oracle_backend(), tensor_device="cpu") == 0
     line = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
@@ -43,6 +44,38 @@ def test_dump_is_the_last_steps_table_and_repeats(tmp_path, capsys, monkeypatch)
     shard = workload.c3_shard(6000, 2500, seed=1, device=torch.device("cpu"), null_fraction=0.01)
     rep = check.compare_result(fetched, check.exact_groups(shard), hash_identity=True)
     assert rep["status"] == "ok" and rep["groups"] == groups > 1000, rep
+
+
+def test_plain_run_times_and_dumps_but_measures_and_checks_nothing_else(tmp_path, capsys, monkeypatch):
+    """Without --full: the contract keys and the same dump as with it, and none of what --full adds is even started."""
+    monkeypatch.setattr(bench, "ROOT", str(tmp_path))
+    argv = ["--gpus", "1", "--rows", "6000", "--batch-rows", "2500", "--steps", "2", "--warmup", "1"]
+    assert bench.main(argv + ["--full", "--dump-outputs", str(tmp_path / "full")], backend=H.oracle_backend(), tensor_device="cpu") == 0
+    full = json.loads([ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")][-1])
+    assert full["check_groups"]["status"] == "ok"
+
+    def never(*a, **kw):
+        raise AssertionError("a plain run went beyond its timed steps")
+    for name in ("cpu_baseline", "host_batch_leg", "measure_traffic", "run_leg"):
+        monkeypatch.setattr(bench, name, never)
+    for name in ("exact_groups", "compare_result"):
+        monkeypatch.setattr(bench.check, name, never)
+    backend = H.oracle_backend()
+    monkeypatch.setattr(backend, "has_profiler", True, raising=False)
+    monkeypatch.setattr(backend, "profiler_enable", never, raising=False)
+    assert bench.main(argv + ["--dump-outputs", str(tmp_path / "plain")], backend=backend, tensor_device="cpu") == 0
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "data"):
+        assert line[k] == full[k], k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["higher_is_better"] is True and line["unit"] == "rows/s"
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] * 1e-3 / 6000 - 1) < 1e-4  # rows / step time
+    assert line["config"]["groups_per_shard"] == full["config"]["groups_per_shard"] > 1000
+    for k in ("check_groups", "check_merged_groups", "reference_host_check", "roofline", "cpu_baseline"):
+        assert line[k] is None, k
+    a, b = _load(tmp_path / "plain"), _load(tmp_path / "full")
+    assert all(np.array_equal(a[k], b[k]) for k in a)
 
 
 def _ascending(a):

@@ -1,19 +1,23 @@
 #!/bin/bash
-# round-end check as the driver runs it: the GPU suite, smoke(), then the default bench line (N = 1)
-cd ${GRAFT_REPO_ROOT:-/root/repo}
-mkdir -p gpurun_out
-timeout 900 python -m pytest tests -m gpu -x -q > gpurun_out/final_pytest.log 2>&1
-echo "pytest rc $?" >> gpurun_out/final_pytest.log
-tail -4 gpurun_out/final_pytest.log
+# round-end check: the GPU suite, smoke(), then the benchmark with everything it measures (N = 1)
+#   bash tools/gpu_final.sh [OUTDIR]      (logs and the bench line land in OUTDIR, default: a fresh temporary directory)
+cd "$(dirname "$0")/.."
+OUT=${1:-$(mktemp -d)}
+mkdir -p "$OUT"
+echo "output in $OUT"
+timeout 900 python -m pytest tests -m gpu -x -q > "$OUT/final_pytest.log" 2>&1
+echo "pytest rc $?" >> "$OUT/final_pytest.log"
+tail -4 "$OUT/final_pytest.log"
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 400 python bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err
+timeout 600 python bench.py --full > "$OUT/final_bench.json" 2> "$OUT/final_bench.err"
 echo "bench rc $?"
-python - <<'PY'
+python - "$OUT/final_bench.json" <<'PY'
 import json
+import sys
 try:
-    d = json.loads(open("gpurun_out/final_bench.json").read().strip().splitlines()[-1])
+    d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
     print({k: d[k] for k in ("value", "ms_per_step")}, d["roofline"]["frac"], d["roofline"].get("traffic"))
-    print({k: (v.get("ms_per_step") if isinstance(v, dict) else v) for k, v in d.get("legs", {}).items()})
+    print(d["summary"].get("legs_ms_per_1B_rows"))
 except Exception as e:
     print("bench line unreadable:", e)
 PY
