@@ -24,6 +24,11 @@ void slow_trace(const char *what, double ms) {
   }
 }
 
+bool hr_trace_enabled() {
+  static const bool on = getenv("ARES_HR_TRACE") != nullptr;
+  return on;
+}
+
 namespace {
 struct PinnedSlot {
   uint64_t *ptr = nullptr;

@@ -27,6 +27,8 @@ class AlgorithmError : public std::runtime_error {
 
 // ARES_RTC_TRACE=<file>: host time of anything that took longer than 5 ms on the calling thread (cold-start diagnostics)
 void slow_trace(const char *what, double ms);
+// ARES_HR_TRACE set (diagnostics, read once): the grouping paths say on stderr what they decided
+bool hr_trace_enabled();
 class SlowScope {
  public:
   explicit SlowScope(const char *what) : what_(what), t0_(std::chrono::steady_clock::now()) {}

@@ -27,6 +27,19 @@ struct DimLayoutD {
   uint16_t valueOff[kMaxDims];  // byte offset of the dim's value vector, in units of `capacity`
 };
 
+// Bytes of one row's values, and of the whole packed row (values + one validity byte per dimension).  Plain sums that cannot
+// fail: make_dim_layout yields the same numbers but throws for layouts it does not hold, and some callers must not throw.
+inline size_t dim_value_bytes(const uint8_t numDimsPerDimWidth[NUM_DIM_WIDTH]) {
+  size_t bytes = 0;
+  for (int w = 0; w < NUM_DIM_WIDTH; w++) bytes += static_cast<size_t>(numDimsPerDimWidth[w]) << (NUM_DIM_WIDTH - 1 - w);
+  return bytes;
+}
+inline size_t dim_row_bytes(const uint8_t numDimsPerDimWidth[NUM_DIM_WIDTH]) {
+  size_t bytes = dim_value_bytes(numDimsPerDimWidth);
+  for (int w = 0; w < NUM_DIM_WIDTH; w++) bytes += numDimsPerDimWidth[w];
+  return bytes;
+}
+
 inline DimLayoutD make_dim_layout(const uint8_t numDimsPerDimWidth[NUM_DIM_WIDTH]) {
   DimLayoutD L;
   memset(&L, 0, sizeof(L));

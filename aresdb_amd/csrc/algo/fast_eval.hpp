@@ -53,6 +53,19 @@ __host__ __device__ inline uint64_t fast_value_bytes(const FastOperands &f, uint
 
 struct __attribute__((packed, aligned(1))) PU16 { uint16_t v; };
 
+// host twin of cvt32 (device_model.hpp) for constants
+inline uint32_t host_cvt32(uint32_t bits, int from, int to) {
+  if (from == to) return bits;
+  auto asf = [](uint32_t b) { float f; memcpy(&f, &b, 4); return f; };
+  auto fb = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
+  switch (to) {
+    case K_BOOL: return from == K_F32 ? (asf(bits) != 0.0f) : (bits != 0u);
+    case K_I32: return from == K_F32 ? static_cast<uint32_t>(static_cast<int32_t>(asf(bits))) : bits;
+    case K_U32: return from == K_F32 ? static_cast<uint32_t>(asf(bits)) : bits;
+    default: return from == K_I32 ? fb(static_cast<float>(static_cast<int32_t>(bits))) : fb(static_cast<float>(bits));
+  }
+}
+
 // x / d and x % d for a divisor that is the same for the whole launch: one multiply-high by
 // M = floor(2^32 / d) estimates the quotient to within one (M = 0 marks d < 2).
 struct FastDivisor {

@@ -466,9 +466,7 @@ void grouped_trim(int device) {
 }
 
 void grouped_note_write(int device, const DimensionVector &v) {
-  size_t rowBytes = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(v.NumDimsPerDimWidth[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
-  if (v.DimValues && v.VectorCapacity > 0) grouped_note_write(device, v.DimValues, rowBytes * static_cast<size_t>(v.VectorCapacity));
+  if (v.DimValues && v.VectorCapacity > 0) grouped_note_write(device, v.DimValues, dim_row_bytes(v.NumDimsPerDimWidth) * static_cast<size_t>(v.VectorCapacity));
 }
 
 namespace {
@@ -592,8 +590,7 @@ int hash_reduce_lds(int device, const DimensionVector &inputKeys, const uint8_t 
     }
 #undef ARES_HR_MERGE_ND
 #undef ARES_HR_MERGE
-    static const bool trace = getenv("ARES_HR_TRACE") != nullptr;  // diagnostics
-    if (trace)
+    if (hr_trace_enabled())  // diagnostics
       fprintf(stderr, "hash_reduce_lds: length %d start %d rows %d streams %d capA %llu capB %u partBits %d -> groups %u overflow %u stale %u\n",
               length, start, rows, streams, static_cast<unsigned long long>(ws.capA), ws.capB, partBits, res.groups, res.overflow, res.stale);
     r.buf->mark_idle();  // read_result waited for the stream behind the last kernel that touches the workspace
@@ -737,8 +734,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
     if (prevSize > 0) grouped_materialize_for_read(device, prevValues, static_cast<size_t>(mw) * prevSize);
   }
   {
-    static const bool trace = getenv("ARES_HR_TRACE") != nullptr;  // diagnostics
-    if (trace)
+    if (hr_trace_enabled())  // diagnostics
       fprintf(stderr, "fused_hash_reduce_run: batch %d prev %d partBits %d | found %d (state: size %d partBits %d ranges %d image %d lazy %d) grouped %d "
                       "| lean %d table %d compact %d narrow %d -> image mode %d knownOut %u\n",
               batchRows, prevSize, partBits, found ? 1 : 0, found ? prev.size : -1, found ? prev.partBits : -1, found && prev.ranges ? 1 : 0,
@@ -930,22 +926,7 @@ struct NotFusable : std::runtime_error {
 
 // Column slots: dimension d -> slot d, measure -> slot ND (a column used twice is simply loaded
 // twice; the second load hits L1).  Filters reuse a slot that already holds their column, or take
-// the one spare slot ND + 1.
-int fused_column(FusedPlanD &plan, const FastOperands &f, int maxCols, bool reuse) {
-  if (reuse)
-    for (int c = 0; c < plan.numCols; c++)
-      if (plan.cols[c].vals == f.vals && plan.cols[c].nulls == f.nulls && plan.cols[c].bitOff == f.bitOff &&
-          plan.cols[c].step == static_cast<uint32_t>(f.step ? f.step : 4))
-        return c;
-  if (plan.numCols >= maxCols) throw NotFusable("too many distinct columns");
-  FusedColumn &col = plan.cols[plan.numCols];
-  col.vals = f.vals;
-  col.nulls = f.nulls;
-  col.bitOff = f.bitOff;
-  col.step = static_cast<uint32_t>(f.step ? f.step : 4);
-  return plan.numCols++;
-}
-
+// the one spare slot ND + 1 (fused_column).
 void fused_expr(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream, FusedPlanD &plan, int maxCols,
                 FusedExpr &out) {
   if (e.arity != 1 && e.arity != 2) throw NotFusable("arity");
@@ -958,7 +939,8 @@ void fused_expr(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStre
   build_params(ins, e.arity, stream, nullptr, nullptr, 0, e.functor, p, temps);
   FastOperands f;
   if (!fast_operands(p, f, compareOnly)) throw NotFusable("expression shape");
-  out.col = fused_column(plan, f, maxCols, compareOnly);
+  out.col = fused_column(plan, f, maxCols, compareOnly ? kFusedReuseFirst : kFusedNoReuse);
+  if (out.col < 0) throw NotFusable("too many distinct columns");
   out.f = f;
   out.f.vals = nullptr;
   out.f.nulls = nullptr;

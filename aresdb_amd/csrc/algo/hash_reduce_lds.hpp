@@ -5,6 +5,7 @@
 
 #include "aggregate.hpp"
 #include "ares_algorithm.h"
+#include "dim_layout.hpp"
 #include "fast_eval.hpp"
 
 namespace ares {
@@ -34,13 +35,10 @@ constexpr int kExtensionFilters = 4;  // AresFusedQuery::filters (include/ares_e
 // beyond it keeps the real Sort + Reduce.
 constexpr int kSortVectorValueBytes = 32;
 inline bool sort_vector_layout_supported(const uint8_t numDimsPerDimWidth[NUM_DIM_WIDTH]) {
-  int nd = 0, valueBytes = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) {
-    nd += numDimsPerDimWidth[w];
-    valueBytes += numDimsPerDimWidth[w] << (NUM_DIM_WIDTH - 1 - w);
-  }
+  int nd = 0;
+  for (int w = 0; w < NUM_DIM_WIDTH; w++) nd += numDimsPerDimWidth[w];
   const bool wide = numDimsPerDimWidth[0] || numDimsPerDimWidth[1];
-  return nd >= 1 && nd <= kFusedDims && (!wide || valueBytes <= kSortVectorValueBytes);
+  return nd >= 1 && nd <= kFusedDims && (!wide || dim_value_bytes(numDimsPerDimWidth) <= static_cast<size_t>(kSortVectorValueBytes));
 }
 struct FusedColumn {
   const uint32_t *vals;
@@ -76,6 +74,93 @@ inline bool fused_plan_narrow(const FusedPlanD &p, int nd) {
   for (int c = 0; c < p.numCols; c++)
     if (fused_col_step(p, c) != 4) return true;
   return false;
+}
+
+// ---- building a plan ------------------------------------------------------------------------------------------------
+// One copy of each decision for everybody who writes a FusedPlanD: the two fusions over a stream's pending work
+// (transform.hip), the fused extension (hash_reduce_lds.hip) and the vector-sourced launchers (hr_rtc.hip).  The struct is
+// memset to zero first; shape_key and the generators read it field by field.
+inline FusedColumn fused_column_of(const FastOperands &f) { return FusedColumn{f.vals, f.nulls, f.bitOff, static_cast<uint32_t>(f.step ? f.step : 4)}; }
+// the expression without what belongs to one launch (the column lives in its slot, the rows come from the scan)
+inline FastOperands fused_strip(FastOperands f) {
+  f.vals = nullptr;
+  f.nulls = nullptr;
+  f.idx = nullptr;
+  f.pad = 0;
+  return f;
+}
+// kind of the value a sink of `dtype` stores
+inline int fused_kind_of(int dtype) { return (dtype == Int32 || dtype == Int16 || dtype == Int8) ? K_I32 : (dtype == Uint32 || dtype == Uint16 || dtype == Uint8) ? K_U32 : K_F32; }
+// The plan's column slot for the operand's column, or a new one behind the slots in use; -1: no room among `maxCols`.
+// A plan may hold one column in several slots (a dimension and the measure of the same column are simply loaded twice; the
+// second load hits L1).  Which of them a filter is given shows in the plan, hence in cache keys and generated sources, and
+// the two kinds of caller have always differed: the extension's filters take the first, a journal's filters the last.
+enum FusedReuse { kFusedNoReuse, kFusedReuseFirst, kFusedReuseLast };
+inline int fused_column(FusedPlanD &plan, const FastOperands &f, int maxCols, FusedReuse reuse) {
+  const FusedColumn col = fused_column_of(f);
+  int found = -1;
+  for (int c = 0; reuse != kFusedNoReuse && c < plan.numCols; c++)
+    if (plan.cols[c].vals == col.vals && plan.cols[c].nulls == col.nulls && plan.cols[c].bitOff == col.bitOff && plan.cols[c].step == col.step &&
+        (found < 0 || reuse == kFusedReuseLast))
+      found = c;
+  if (found >= 0) return found;
+  if (plan.numCols >= maxCols) return -1;
+  plan.cols[plan.numCols] = col;
+  return plan.numCols++;
+}
+// Dimension d is what a queued transform would have written into the vector's slot d (`width` bytes): column slot d.
+inline void fused_plan_dim(FusedPlanD &plan, int d, const FastOperands &f, const SinkD &sink, int width) {
+  plan.cols[d] = fused_column_of(f);
+  plan.dims[d].f = fused_strip(f);
+  plan.dims[d].col = d;
+  plan.dims[d].outKind = fused_kind_of(sink.dtype);
+  plan.dimWidth[d] = static_cast<uint8_t>(width);
+}
+// The measure is what a queued transform would have written into the measure vector: column slot nd.
+inline void fused_plan_measure(FusedPlanD &plan, int nd, const FastOperands &f, const SinkD &sink, int valueBytes) {
+  plan.cols[nd] = fused_column_of(f);
+  plan.measure.f = fused_strip(f);
+  plan.measure.col = nd;
+  plan.measure.outKind = fused_kind_of(sink.dtype);
+  plan.measureDtype = sink.dtype;
+  plan.measureWidth = valueBytes;
+  plan.identity = sink.identity;
+  plan.numCols = nd + 1;
+}
+// ... or a constant (Sort + Reduce: COUNT(*)): no column
+inline void fused_plan_const_measure(FusedPlanD &plan, int nd, uint64_t constBits, int dtype, int valueBytes) {
+  plan.measure.col = -1;
+  plan.measure.f.bbits = static_cast<uint32_t>(constBits);  // (what the scan's records carry; the merge takes constBits)
+  plan.measureDtype = dtype;
+  plan.measureWidth = valueBytes;
+  plan.numCols = nd;
+}
+// The filters of a journal, after dimensions and measure: each reuses a slot that holds its column or takes a spare one.
+// false: more filters or columns than a plan holds.
+inline bool fused_plan_filters(FusedPlanD &plan, const FastOperands *filters, size_t count) {
+  if (count > static_cast<size_t>(kFusedFilters)) return false;
+  for (size_t k = 0; k < count; k++) {
+    const int col = fused_column(plan, filters[k], kFusedCols, kFusedReuseLast);
+    if (col < 0) return false;
+    plan.filters[k].f = fused_strip(filters[k]);
+    plan.filters[k].col = col;
+    plan.filters[k].outKind = K_BOOL;
+  }
+  plan.numFilters = static_cast<int>(count);
+  return true;
+}
+// Column slot d = rows [rowBase, ..) of dimension d of a materialised dimension vector (`widths`: bytes per slot in vector
+// order, null = all four bytes); slot nd, the measure's, is the caller's.
+inline void fused_plan_vector_columns(FusedPlanD &plan, const uint8_t *dimValues, size_t capacity, int nd, const int *widths, uint32_t rowBase) {
+  plan.numCols = nd + 1;
+  size_t valueBytes = 0, off = 0;
+  for (int d = 0; d < nd; d++) valueBytes += static_cast<size_t>(widths ? widths[d] : 4);
+  for (int d = 0; d < nd; d++) {
+    const size_t w = static_cast<size_t>(widths ? widths[d] : 4);
+    plan.cols[d].vals = reinterpret_cast<const uint32_t *>(dimValues + off * capacity + w * rowBase);
+    plan.cols[d].nulls = dimValues + valueBytes * capacity + static_cast<size_t>(d) * capacity + rowBase;
+    off += w;
+  }
 }
 
 // Column slots of a plan of ND dimensions: dimension d -> slot d, measure -> slot ND; a filter reuses

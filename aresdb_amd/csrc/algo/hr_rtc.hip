@@ -107,19 +107,6 @@ const RtcApi &rtc_api() {
   return api;
 }
 
-// host twin of cvt32 (device_model.hpp) for constants
-uint32_t host_cvt32(uint32_t bits, int from, int to) {
-  if (from == to) return bits;
-  auto asf = [](uint32_t b) { float f; memcpy(&f, &b, 4); return f; };
-  auto fb = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
-  switch (to) {
-    case K_BOOL: return from == K_F32 ? (asf(bits) != 0.0f) : (bits != 0u);
-    case K_I32: return from == K_F32 ? static_cast<uint32_t>(static_cast<int32_t>(asf(bits))) : bits;
-    case K_U32: return from == K_F32 ? static_cast<uint32_t>(asf(bits)) : bits;
-    default: return from == K_I32 ? fb(static_cast<float>(static_cast<int32_t>(bits))) : fb(static_cast<float>(bits));
-  }
-}
-
 bool int_kind(int k) { return k == K_I32 || k == K_U32; }
 bool col_kind(int k) { return k == K_I32 || k == K_U32 || k == K_F32; }
 
@@ -198,15 +185,17 @@ uint32_t compare_const(const FastOperands &f) { return host_cvt32(f.bbits, f.bki
 
 bool plain_store(int rk, int outKind) { return rk == outKind || (rk != K_F32 && outKind != K_F32 && rk != K_BOOL); }
 
+}  // namespace
 // ARES_HR_PHASES=1: the generated kernels time-stamp their phases (diagnostics; a different source text, so
 // a separate cache entry)
-static bool phases_enabled() {
+bool phases_enabled() {
   static const bool on = [] {
     const char *e = getenv("ARES_HR_PHASES");
     return e && e[0] == '1';
   }();
   return on;
 }
+namespace {
 
 struct RtcArgs {  // mirrors `struct Args` of the generated source (args_text below): pointers, 8-byte, then 4-byte fields
   const uint32_t *vals[kFusedCols];
@@ -2352,11 +2341,7 @@ void rtc_vector_scan_launch(const RtcKernel &kernel, const uint8_t *dimValues, s
                             uint32_t rowBase, int length, const hr::Workspace &ws, hipStream_t stream) {
   FusedPlanD plan;
   memset(&plan, 0, sizeof(plan));
-  plan.numCols = nd + 1;
-  for (int d = 0; d < nd; d++) {
-    plan.cols[d].vals = reinterpret_cast<const uint32_t *>(dimValues + 4ull * d * capacity) + rowBase;
-    plan.cols[d].nulls = dimValues + 4ull * nd * capacity + static_cast<size_t>(d) * capacity + rowBase;
-  }
+  fused_plan_vector_columns(plan, dimValues, capacity, nd, nullptr, rowBase);
   plan.cols[nd].vals = reinterpret_cast<const uint32_t *>(values + static_cast<size_t>(vw) * rowBase);
   RtcArgs args;
   fill_scan_args(args, plan, rowBase, length, ws);
@@ -2374,15 +2359,7 @@ void rtc_sort_vector_scan_launch(const RtcKernel &kernel, const uint8_t *dimValu
                                  hipStream_t stream) {
   FusedPlanD plan;
   memset(&plan, 0, sizeof(plan));
-  plan.numCols = nd + 1;
-  size_t valueBytes = 0, off = 0;
-  for (int d = 0; d < nd; d++) valueBytes += static_cast<size_t>(widths ? widths[d] : 4);
-  for (int d = 0; d < nd; d++) {
-    const size_t w = static_cast<size_t>(widths ? widths[d] : 4);
-    plan.cols[d].vals = reinterpret_cast<const uint32_t *>(dimValues + off * capacity + w * rowBase);
-    plan.cols[d].nulls = dimValues + valueBytes * capacity + static_cast<size_t>(d) * capacity + rowBase;
-    off += w;
-  }
+  fused_plan_vector_columns(plan, dimValues, capacity, nd, widths, rowBase);
   plan.cols[nd].vals = reinterpret_cast<const uint32_t *>(values) + rowBase;  // (8-byte values: read at this stride and ignored)
   RtcArgs args;
   fill_scan_args(args, plan, rowBase, length, ws);
@@ -2400,15 +2377,7 @@ void rtc_hll_scan_launch(const RtcKernel &kernel, const uint8_t *dimValues, size
                          uint32_t rowBase, int length, const hr::Workspace &ws, hipStream_t stream) {
   FusedPlanD plan;
   memset(&plan, 0, sizeof(plan));
-  plan.numCols = nd + 1;
-  size_t valueBytes = 0, off = 0;
-  for (int d = 0; d < nd; d++) valueBytes += static_cast<size_t>(widths ? widths[d] : 4);
-  for (int d = 0; d < nd; d++) {
-    const size_t w = static_cast<size_t>(widths ? widths[d] : 4);
-    plan.cols[d].vals = reinterpret_cast<const uint32_t *>(dimValues + off * capacity + w * rowBase);
-    plan.cols[d].nulls = dimValues + valueBytes * capacity + static_cast<size_t>(d) * capacity + rowBase;
-    off += w;
-  }
+  fused_plan_vector_columns(plan, dimValues, capacity, nd, widths, rowBase);
   plan.cols[nd].vals = hllValues;  // (entry i of the batch is dimension row rowBase + i)
   RtcArgs args;
   fill_scan_args(args, plan, rowBase, length, ws);

@@ -22,6 +22,8 @@ struct Widen;
 struct RtcEntry;
 using RtcKernel = std::shared_ptr<RtcEntry>;
 
+// ARES_HR_PHASES=1 (diagnostics, read once): the generated kernels and the Sort + Reduce merges time-stamp their phases
+bool phases_enabled();
 // hiprtc could be loaded (and ARES_RTC is not 0)
 bool rtc_scan_available();
 // workgroups (= private record streams per partition) for a batch of `rows` rows

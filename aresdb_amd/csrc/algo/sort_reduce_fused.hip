@@ -911,12 +911,6 @@ std::shared_ptr<uint64_t> take_key_block(int device, size_t groups, hipStream_t 
   });
 }
 
-size_t dim_row_bytes(const uint8_t ndw[NUM_DIM_WIDTH]) {
-  size_t rowBytes = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(ndw[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
-  return rowBytes;
-}
-
 std::shared_ptr<uint64_t> sorted_state_lookup(int device, const DimensionVector &v, const uint8_t *values, int valueBytes, int size) {
   if (!sorted_state_enabled() || size <= 0) return nullptr;
   std::lock_guard<std::mutex> lock(g_sortedMutex);
@@ -973,9 +967,9 @@ void sorted_state_note_write(int device, const void *ptr, size_t bytes) {
     auto hit = [&](const uint8_t *a, size_t n) { return a < hi && lo < a + n; };
     bool touched = st.device == device && hit(st.values, static_cast<size_t>(st.valueBytes) * st.size);
     if (st.device == device && !touched) {
-      size_t off = 0, valueBytes = 0;
+      size_t off = 0;
+      const size_t valueBytes = dim_value_bytes(st.ndw);
       int nd = 0;
-      for (int w = 0; w < NUM_DIM_WIDTH; w++) valueBytes += static_cast<size_t>(st.ndw[w]) << (NUM_DIM_WIDTH - 1 - w);
       for (int w = 0; w < NUM_DIM_WIDTH && !touched; w++) {
         const size_t width = static_cast<size_t>(1) << (NUM_DIM_WIDTH - 1 - w);
         for (int k = 0; k < st.ndw[w] && !touched; k++) {
@@ -989,6 +983,50 @@ void sorted_state_note_write(int device, const void *ptr, size_t bytes) {
     else i++;
   }
 }
+namespace {
+// ARES_HR_PHASES=1 (diagnostics): the merge kernels of both layouts leave time stamps per partition (100 MHz clock): slot 5 on
+// entry, slot 0 once the table is clear, slots 1 .. 4 behind init, previous groups, records and order.
+// merge_phase_stamps: the buffer for MergeArgs::phases, cleared on `stream` ahead of the merge (null: switched off);
+// merge_phase_report: what they say, once the call has waited for the stream (its read-back).
+uint64_t *merge_phase_stamps(int numParts, hipStream_t stream) {
+  if (!phases_enabled()) return nullptr;
+  static uint64_t *phases = nullptr;
+  if (!phases) hip_check(hipMalloc(reinterpret_cast<void **>(&phases), sizeof(uint64_t) * 8 << kWideMaxPartBits), "hipMalloc");
+  hip_check(hipMemsetAsync(phases, 0, sizeof(uint64_t) * 8 * numParts, stream), "hipMemsetAsync");
+  return phases;
+}
+void merge_phase_report(const uint64_t *phases, int numParts, const char *label, int prevSize, int batchRows) {
+  if (!phases) return;  // where a partition's time goes
+  static int launches = 0;
+  std::vector<uint64_t> h(static_cast<size_t>(8) * numParts);
+  hip_check(hipMemcpy(h.data(), phases, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost), "hipMemcpy");
+  if (++launches > 6 && launches % 16 != 0) return;
+  double sum[4] = {0, 0, 0, 0}, resident = 0;
+  uint64_t first = ~0ull, last = 0;
+  for (int p = 0; p < numParts; p++) {
+    const uint64_t *t = &h[static_cast<size_t>(8) * p];
+    if (t[5] < first) first = t[5];
+    if (t[4] > last) last = t[4];
+    for (int k = 0; k < 4; k++) sum[k] += static_cast<double>(t[k + 1] - t[k]) * 0.01;
+    resident += static_cast<double>(t[4] - t[5]) * 0.01;
+  }
+  const double span = static_cast<double>(last - first) * 0.01;
+  std::vector<double> ends, lives;
+  for (int p = 0; p < numParts; p++) {
+    ends.push_back(static_cast<double>(h[static_cast<size_t>(8) * p + 4] - first) * 0.01);
+    lives.push_back(static_cast<double>(h[static_cast<size_t>(8) * p + 4] - h[static_cast<size_t>(8) * p + 5]) * 0.01);
+  }
+  std::sort(ends.begin(), ends.end());
+  std::sort(lives.begin(), lives.end());
+  auto q = [&](const std::vector<double> &v, double f) { return v[static_cast<size_t>(f * (v.size() - 1))]; };
+  fprintf(stderr, "  workgroups done by: 50%% %.0f us, 90%% %.0f, 99%% %.0f, 100%% %.0f; lifetimes: median %.1f us, 90%% %.1f, 99%% %.1f, max %.1f; first starts spread %.0f us\n",
+          q(ends, 0.5), q(ends, 0.9), q(ends, 0.99), q(ends, 1.0), q(lives, 0.5), q(lives, 0.9), q(lives, 0.99), q(lives, 1.0),
+          static_cast<double>(h[5 + 8 * static_cast<size_t>(numParts - 1)] - first) * 0.01);
+  fprintf(stderr, "%s phases (launch %d, %d partitions, prev %d, batch %d): span %.1f us, %.0f workgroups resident on average; per partition avg: clear %.1f + init %.1f + previous groups %.1f + records %.1f + order %.1f us\n",
+          label, launches, numParts, prevSize, batchRows, span, resident / span, resident / numParts - (sum[0] + sum[1] + sum[2] + sum[3]) / numParts, sum[0] / numParts,
+          sum[1] / numParts, sum[2] / numParts, sum[3] / numParts);
+}
+}  // namespace
 
 bool fused_sort_reduce_enabled() {
   static EnvSwitch<bool> on("ARES_SORT_FUSE", [](const char *e) { return !(e && e[0] == '0'); });
@@ -1091,16 +1129,7 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
     ARES_LAUNCH("sr_prev_kernel", sr_prev_kernel, grid, 256, stream, m, L, ws.recA);
   }
   rtc_sort_scan_launch(scan, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
-  static const bool phasesOn = [] {
-    const char *e = getenv("ARES_HR_PHASES");
-    return e && e[0] == '1';
-  }();
-  static uint64_t *phases = nullptr;
-  if (phasesOn) {
-    if (!phases) hip_check(hipMalloc(reinterpret_cast<void **>(&phases), sizeof(uint64_t) * 8 * kMaxPartitions), "hipMalloc");
-    hip_check(hipMemsetAsync(phases, 0, sizeof(uint64_t) * 8 * kMaxPartitions, stream), "hipMemsetAsync");
-    m.phases = phases;
-  }
+  m.phases = merge_phase_stamps(numParts, stream);
   if (vw == 8) {
     ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false>), numParts, kThreads, stream, m);
     ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<8, false>), numParts, kThreads, stream, m, plan, L);
@@ -1110,26 +1139,9 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
   }
   uint32_t w[3] = {0, 0, 0};
   read_back_u32(ws.outCount, w, 3, stream);
-  if (phasesOn) {  // diagnostics: where a partition's time goes
-    static int launches = 0;
-    std::vector<uint64_t> h(static_cast<size_t>(8) * numParts);
-    hip_check(hipMemcpy(h.data(), phases, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-    if (++launches <= 4 || launches % 16 == 0) {
-      double sum[4] = {0, 0, 0, 0};
-      uint64_t first = ~0ull, last = 0;
-      for (int p = 0; p < numParts; p++) {
-        const uint64_t *t = &h[static_cast<size_t>(8) * p];
-        if (t[0] < first) first = t[0];
-        if (t[4] > last) last = t[4];
-        for (int k = 0; k < 4; k++) sum[k] += static_cast<double>(t[k + 1] - t[k]) * 0.01;
-      }
-      fprintf(stderr, "sr_merge_kernel phases (launch %d, %d partitions, prev %d, batch %d): span %.1f us; per partition avg: init %.1f + previous groups %.1f + records %.1f + order %.1f us\n",
-              launches, numParts, prevSize, batchRows, static_cast<double>(last - first) * 0.01, sum[0] / numParts, sum[1] / numParts, sum[2] / numParts, sum[3] / numParts);
-    }
-  }
+  merge_phase_report(m.phases, numParts, "sr_merge_kernel", prevSize, batchRows);
   buf.mark_idle();
-  static const bool trace = getenv("ARES_HR_TRACE") != nullptr;  // diagnostics
-  if (trace)
+  if (hr_trace_enabled())  // diagnostics
     fprintf(stderr, "fused_sort_reduce_run: batch %d prev %d partBits %d streams %d capA %llu capB %u vw %d const %d -> groups %u overflow %u emptykey %u\n",
             batchRows, prevSize, partBits, streams, static_cast<unsigned long long>(capA), capB, vw, constMeasure ? 1 : 0, w[0], w[1], w[2]);
   // a record stream may have overflowed (sorted rows fill a chunk's partitions unevenly): more room — kept for the process — and again
@@ -1158,7 +1170,7 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
 // integer aggregates of 4 or 8 bytes; returns like fused_sort_reduce_run.
 static int sort_reduce_vectors_run(int device, int length, const DimensionVector &in, const uint8_t *inValues, const DimensionVector &out,
                                    uint8_t *outValues, const AggSpec &a, hipStream_t stream, int slack, bool spread) {
-  static const bool trace = getenv("ARES_HR_TRACE") != nullptr;  // diagnostics
+  const bool trace = hr_trace_enabled();  // diagnostics
   auto decline = [&](const char *why) {
     if (trace) fprintf(stderr, "fused_sort_reduce_vectors: rows %d declined: %s\n", length, why);
     return kFusedUnavailable;
@@ -1295,16 +1307,7 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
   } else {
     hip_check(hipMemsetAsync(offsets2, 0, partBytes, stream), "hipMemsetAsync");
   }
-  static const bool phasesOn = [] {
-    const char *e = getenv("ARES_HR_PHASES");
-    return e && e[0] == '1';
-  }();
-  static uint64_t *phases = nullptr;
-  if (phasesOn) {
-    if (!phases) hip_check(hipMalloc(reinterpret_cast<void **>(&phases), sizeof(uint64_t) * 8 << kWideMaxPartBits), "hipMalloc");
-    hip_check(hipMemsetAsync(phases, 0, sizeof(uint64_t) * 8 * numParts, stream), "hipMemsetAsync");
-    m.phases = phases;
-  }
+  m.phases = merge_phase_stamps(numParts, stream);
   FusedPlanD noPlan;
   memset(&noPlan, 0, sizeof(noPlan));
   if (vw == 8) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, true>), numParts, T::kLanes, stream, m);
@@ -1314,39 +1317,7 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
   else ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<4, true>), numParts, T::kLanes, stream, m, noPlan, L);
   uint32_t w[4] = {0, 0, 0, 0};
   read_back_u32(flags, w, 4, stream);
-  if (phasesOn) {  // diagnostics: where a partition's time goes
-    static int launches = 0;
-    std::vector<uint64_t> h(static_cast<size_t>(8) * numParts);
-    hip_check(hipMemcpy(h.data(), phases, sizeof(uint64_t) * h.size(), hipMemcpyDeviceToHost), "hipMemcpy");
-    if (++launches <= 6 || launches % 16 == 0) {
-      double sum[4] = {0, 0, 0, 0}, resident = 0;
-      uint64_t first = ~0ull, last = 0;
-      for (int p = 0; p < numParts; p++) {
-        const uint64_t *t = &h[static_cast<size_t>(8) * p];
-        if (t[5] < first) first = t[5];
-        if (t[4] > last) last = t[4];
-        for (int k = 0; k < 4; k++) sum[k] += static_cast<double>(t[k + 1] - t[k]) * 0.01;
-        resident += static_cast<double>(t[4] - t[5]) * 0.01;
-      }
-      const double span = static_cast<double>(last - first) * 0.01;
-      {
-        std::vector<double> ends, lives;
-        for (int p = 0; p < numParts; p++) {
-          ends.push_back(static_cast<double>(h[static_cast<size_t>(8) * p + 4] - first) * 0.01);
-          lives.push_back(static_cast<double>(h[static_cast<size_t>(8) * p + 4] - h[static_cast<size_t>(8) * p + 5]) * 0.01);
-        }
-        std::sort(ends.begin(), ends.end());
-        std::sort(lives.begin(), lives.end());
-        auto q = [&](const std::vector<double> &v, double f) { return v[static_cast<size_t>(f * (v.size() - 1))]; };
-        fprintf(stderr, "  workgroups done by: 50%% %.0f us, 90%% %.0f, 99%% %.0f, 100%% %.0f; lifetimes: median %.1f us, 90%% %.1f, 99%% %.1f, max %.1f; first starts spread %.0f us\n",
-                q(ends, 0.5), q(ends, 0.9), q(ends, 0.99), q(ends, 1.0), q(lives, 0.5), q(lives, 0.9), q(lives, 0.99), q(lives, 1.0),
-                static_cast<double>(h[5 + 8 * static_cast<size_t>(numParts - 1)] - first) * 0.01);
-      }
-      fprintf(stderr, "sr_merge_kernel<wide> phases (launch %d, %d partitions, prev %d, batch %d): span %.1f us, %.0f workgroups resident on average; per partition avg: clear %.1f + init %.1f + previous groups %.1f + records %.1f + order %.1f us\n",
-              launches, numParts, prevSize, batchRows, span, resident / span, resident / numParts - (sum[0] + sum[1] + sum[2] + sum[3]) / numParts, sum[0] / numParts,
-              sum[1] / numParts, sum[2] / numParts, sum[3] / numParts);
-    }
-  }
+  merge_phase_report(m.phases, numParts, "sr_merge_kernel<wide>", prevSize, batchRows);
   buf.mark_idle();
   if (trace)
     fprintf(stderr, "fused_sort_reduce_vectors: rows %d prev %d (hashes %s) partBits %d/%d%s streams %d cap1 %u -> groups %u stream overflow %u table overflow %u emptykey %u\n",

@@ -695,11 +695,7 @@ static bool sort_touches(const PendingSort &s, const ByteRange &r) {
     const uint8_t *lo = static_cast<const uint8_t *>(p);
     return p && bytes && lo < r.hi && r.lo < lo + bytes;
   };
-  auto vector_bytes = [](const DimensionVector &v) {
-    size_t rowBytes = 0;
-    for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(v.NumDimsPerDimWidth[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
-    return rowBytes * static_cast<size_t>(v.VectorCapacity > 0 ? v.VectorCapacity : 0);
-  };
+  auto vector_bytes = [](const DimensionVector &v) { return dim_row_bytes(v.NumDimsPerDimWidth) * static_cast<size_t>(v.VectorCapacity > 0 ? v.VectorCapacity : 0); };
   const size_t n = static_cast<size_t>(s.length > 0 ? s.length : 0);
   bool any = hit(s.keys.DimValues, vector_bytes(s.keys)) || hit(s.keys.HashValues, 8 * n) || hit(s.keys.IndexVector, 4 * n);
   if (s.reduced)
@@ -842,8 +838,7 @@ bool virtual_iota_peek(int device, const uint32_t *indexVector, int n, bool cons
 void settle_dimension_vector(int device, const DimensionVector &v, bool rowsOnly) {
   if (!defer_available()) return;
   const size_t cap = v.VectorCapacity > 0 ? static_cast<size_t>(v.VectorCapacity) : 0;
-  size_t rowBytes = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(v.NumDimsPerDimWidth[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
+  const size_t rowBytes = dim_row_bytes(v.NumDimsPerDimWidth);
   materialize_fills_for_read(device, v.DimValues, rowBytes * cap);
   if (rowsOnly) return;  // (the caller is about to DEFINE the hash and index vector: define_lazy_sort_vectors)
   materialize_fills_for_read(device, v.HashValues, 8 * cap);
@@ -925,8 +920,7 @@ static void flush_deferred_impl(int device, const ByteRange *limboA, const ByteR
 void flush_deferred(int device) { flush_deferred_impl(device, nullptr, nullptr); }
 
 void flush_deferred_for_vector(int device, const DimensionVector &v, const void *values, size_t valueBytes) {
-  size_t rowBytes = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(v.NumDimsPerDimWidth[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
+  const size_t rowBytes = dim_row_bytes(v.NumDimsPerDimWidth);
   flush_deferred_for_inputs(device, v.DimValues, rowBytes * static_cast<size_t>(v.VectorCapacity > 0 ? v.VectorCapacity : 0),
                             values, valueBytes);
 }
@@ -1317,19 +1311,6 @@ static void note_sink(int device, const SinkD &s, int n) {
   if (n <= 0) return;
   mem_note_write(device, s.values, static_cast<size_t>(s.width) * n);
   if (s.nulls) mem_note_write(device, s.nulls, static_cast<size_t>(n));
-}
-
-// host twin of cvt32 (device_model.hpp)
-static uint32_t host_cvt32(uint32_t bits, int from, int to) {
-  if (from == to) return bits;
-  auto asf = [](uint32_t b) { float f; memcpy(&f, &b, 4); return f; };
-  auto fb = [](float f) { uint32_t b; memcpy(&b, &f, 4); return b; };
-  switch (to) {
-    case K_BOOL: return from == K_F32 ? (asf(bits) != 0.0f) : (bits != 0u);
-    case K_I32: return from == K_F32 ? static_cast<uint32_t>(static_cast<int32_t>(asf(bits))) : bits;
-    case K_U32: return from == K_F32 ? static_cast<uint32_t>(asf(bits)) : bits;
-    default: return from == K_I32 ? fb(static_cast<float>(static_cast<int32_t>(bits))) : fb(static_cast<float>(bits));
-  }
 }
 
 // What store_measure32 (device_model.hpp) stores for every row of `Noop(constant)`: host twin, run length 1.
@@ -2145,166 +2126,11 @@ void launch_pending_writers(int device, const void *ptr, size_t bytes) {
   released.run(device);
 }
 
-// HashReduce's first move: when the stream's pending queue is exactly "the dimension columns and the
-// measure of rows [prev, prev + n) of inputKeys / inputValues", evaluate it on the fly (the fused
-// scan of hash_reduce_lds.hip) instead of launching it.  Returns false when the call must take the
-// ordinary path (whatever was pending has been launched, in stream order).
-bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const DimensionVector &in, const uint8_t *inValues,
-                                   const DimensionVector &out, uint8_t *outValues, int valueBytes, int length, int aggFunc,
-                                   int *groups) {
-  if (!fuse_available()) return false;
-  const bool forcedGlobal = global_table_forced();
-  PendingQueue q;
-  FusedPlanD plan;
-  memset(&plan, 0, sizeof(plan));
-  int nd = 0, prev = 0, n0 = 0;
-  AggSpec a;
-  {
-    DeferLock lock(device);
-    auto it = t_state->pending.find({device, stream});
-    if (it == t_state->pending.end() || it->second.jobs.count == 0) return false;
-    PendingQueue &pq = it->second;
-    bool ok = !forcedGlobal;
-    // dimension slots of 4, 2 or 1 bytes, in the vector's (descending width) order
-    nd = in.NumDimsPerDimWidth[2] + in.NumDimsPerDimWidth[3] + in.NumDimsPerDimWidth[4];
-    for (int k = 0; k < NUM_DIM_WIDTH; k++)
-      ok = ok && (k >= 2 || in.NumDimsPerDimWidth[k] == 0) && out.NumDimsPerDimWidth[k] == in.NumDimsPerDimWidth[k];
-    ok = ok && nd >= 1 && nd <= kFusedDims && pq.jobs.count == nd + 1;
-    DimLayoutD L;
-    memset(&L, 0, sizeof(L));
-    if (ok) L = make_dim_layout(in.NumDimsPerDimWidth);
-    prev = length - pq.n;
-    ok = ok && prev >= 0 && pq.n > 0;
-    if (ok) {
-      try {
-        a = make_agg_spec(aggFunc, valueBytes);
-        ok = hash_reduce_lds_supported(a);
-      } catch (std::exception &) {
-        ok = false;
-      }
-    }
-    // survivors: the whole batch (no filter ran) or what the journalled filters keep
-    const FilterJournal *journal = nullptr;
-    n0 = pq.n;
-    if (ok && pq.idx) {
-      auto j = t_state->journals.find(pq.idx);
-      ok = j != t_state->journals.end() && j->second.valid && j->second.start == 0 && j->second.device == device;
-      if (ok) {
-        journal = &j->second;
-        n0 = journal->n0;
-      }
-    }
-    // every dimension column and the measure of rows [prev, prev + n) must be a pending sink
-    const size_t cap = static_cast<size_t>(in.VectorCapacity);
-    int dimJob[kFusedDims], measureJob = -1;
-    for (int c = 0; c < kFusedDims; c++) dimJob[c] = -1;
-    for (int k = 0; ok && k < pq.jobs.count; k++) {
-      const SinkD &s = pq.jobs.s[k];
-      ok = pq.colRows[k] >= static_cast<uint32_t>(n0);
-      if (s.type == SINK_MEASURE) {
-        ok = ok && measureJob < 0 && s.values == inValues + static_cast<size_t>(valueBytes) * prev && s.width == valueBytes &&
-             s.agg == aggFunc && s.baseCounts == nullptr;
-        measureJob = k;
-      } else {
-        int d = -1;
-        for (int c = 0; c < nd; c++)
-          if (s.values == in.DimValues + static_cast<size_t>(L.valueOff[c]) * cap + static_cast<size_t>(L.width[c]) * prev &&
-              s.nulls == in.DimValues + static_cast<size_t>(L.valueBytes) * cap + cap * c + prev && s.width == L.width[c])
-            d = c;
-        ok = ok && s.type == SINK_DIM && d >= 0 && dimJob[d] < 0;
-        if (ok) dimJob[d] = k;
-      }
-    }
-    ok = ok && measureJob >= 0;
-    for (int c = 0; ok && c < nd; c++) ok = dimJob[c] >= 0;
-    if (ok) {
-      auto column_of = [](const FastOperands &f) { return FusedColumn{f.vals, f.nulls, f.bitOff, static_cast<uint32_t>(f.step ? f.step : 4)}; };
-      auto strip = [](FastOperands f) {
-        f.vals = nullptr;
-        f.nulls = nullptr;
-        f.idx = nullptr;
-        f.pad = 0;
-        return f;
-      };
-      auto kind_of = [](int dtype) { return (dtype == Int32 || dtype == Int16 || dtype == Int8) ? K_I32 : (dtype == Uint32 || dtype == Uint16 || dtype == Uint8) ? K_U32 : K_F32; };
-      for (int c = 0; c < nd; c++) {
-        const int k = dimJob[c];
-        plan.cols[c] = column_of(pq.jobs.f[k]);
-        plan.dims[c].f = strip(pq.jobs.f[k]);
-        plan.dims[c].col = c;
-        plan.dims[c].outKind = kind_of(pq.jobs.s[k].dtype);
-        plan.dimWidth[c] = L.width[c];
-      }
-      plan.cols[nd] = column_of(pq.jobs.f[measureJob]);
-      plan.measure.f = strip(pq.jobs.f[measureJob]);
-      plan.measure.col = nd;
-      plan.measure.outKind = kind_of(pq.jobs.s[measureJob].dtype);
-      plan.measureDtype = pq.jobs.s[measureJob].dtype;
-      plan.measureWidth = valueBytes;
-      plan.identity = pq.jobs.s[measureJob].identity;
-      plan.numCols = nd + 1;
-      ok = !(valueBytes == 8 && plan.identity != 0);  // records carry 4 bytes: a null must widen to the identity
-      if (journal) {
-        ok = ok && journal->filters.size() <= static_cast<size_t>(kFusedFilters);
-        for (size_t k = 0; ok && k < journal->filters.size(); k++) {
-          const FastOperands &f = journal->filters[k];
-          ok = journal->colRows[k] >= static_cast<uint32_t>(n0);
-          int col = -1;
-          for (int c = 0; c < plan.numCols; c++)
-            if (plan.cols[c].vals == f.vals && plan.cols[c].nulls == f.nulls && plan.cols[c].bitOff == f.bitOff &&
-                plan.cols[c].step == static_cast<uint32_t>(f.step ? f.step : 4))
-              col = c;
-          if (col < 0 && plan.numCols < kFusedCols) {
-            col = plan.numCols++;
-            plan.cols[col] = column_of(f);
-          }
-          ok = ok && col >= 0;
-          plan.filters[k].f = strip(f);
-          plan.filters[k].col = col;
-          plan.filters[k].outKind = K_BOOL;
-        }
-        plan.numFilters = static_cast<int>(journal->filters.size());
-      }
-      // the precompiled generic scan holds nd + 2 column slots; a narrow plan only ever runs on generated kernels (kFusedCols)
-      ok = ok && (plan.numCols <= nd + 2 || fused_plan_narrow(plan, nd));
-    }
-    if (!ok) {  // the ordinary path: the pending work runs now, ahead of this call on the same stream
-      launch_queue(stream, pq, /*inOrder=*/true);
-      g_releaseHeld(device, hold_tag(stream));
-      return false;
-    }
-    q = pq;  // taken out of the queue: nobody else launches it
-    pq.jobs.count = 0;
-    pq.reads.clear();
-    pq.writes.clear();
-    pq.keep.clear();  // (the copy holds the decoded columns from here on: left in place they piled up, two per batch, for the life
-                      // of the stream — 86 GB after 143 archive batches — and every later copy of the queue took the pile along)
-    pq.overWait = false;
-    if (q.idx) {  // (decoded columns only the filters read live as long as the consumed queue does: the scan is launched below)
-      auto jk = t_state->journals.find(q.idx);
-      if (jk != t_state->journals.end()) q.keep.insert(q.keep.end(), jk->second.keep.begin(), jk->second.keep.end());
-      t_state->journals.erase(q.idx);
-    }
-  }
-  DimensionVector prevKeys = in;
-  const int result = fused_hash_reduce_run(device, plan, n0, prevKeys, inValues, prev, out, outValues, a, stream);
-  DeferLock lock(device);
-  if (result < 0) {  // a partition region overflowed, or the call was declined: materialise the inputs after all
-    launch_queue(stream, q, /*inOrder=*/true);
-    lock.unlock();
-    g_releaseHeld(device, hold_tag(stream));
-    return false;
-  }
-  t_state->limbo[{device, stream}] = q;  // launchable until the next batch begins (begin_batch)
-  *groups = result;
-  return true;
-}
-
-// ---- Sort + Reduce over pending transforms (sort_reduce_fused.hip) ---------------------------------------------------------
+// ---- a stream's pending work as a fused plan: what HashReduce and Sort + Reduce share ---------------------------------
 namespace {
 // The queue `pq` is "the dimension columns [and the measure] of rows [prev, prev + pq.n) of `in`": which job writes which
 // dimension, which one the measure (-1: none queued).  Caller holds the device's DeferLock.
-bool match_sort_jobs(const PendingQueue &pq, const DimensionVector &in, const DimLayoutD &L, int prev, int (&dimJob)[kFusedDims], int *measureJob) {
+bool match_jobs(const PendingQueue &pq, const DimensionVector &in, const DimLayoutD &L, int prev, int (&dimJob)[kFusedDims], int *measureJob) {
   const int nd = L.numDims;
   const size_t cap = static_cast<size_t>(in.VectorCapacity);
   if (nd < 1 || nd > kFusedDims || in.NumDimsPerDimWidth[0] || in.NumDimsPerDimWidth[1]) return false;
@@ -2330,6 +2156,139 @@ bool match_sort_jobs(const PendingQueue &pq, const DimensionVector &in, const Di
     if (dimJob[c] < 0) return false;
   return true;
 }
+// the queued measure is this call's: its rows, its width, its aggregate
+bool measure_job_matches(const SinkD &s, const uint8_t *measureRows, int valueBytes, int aggFunc) {
+  return s.values == measureRows && s.width == valueBytes && s.agg == aggFunc &&
+         !(valueBytes == 8 && s.identity != 0);  // records carry 4 bytes: a null must widen to the identity
+}
+// survivors of the queue's rows: the whole batch (no filter ran: no journal, n0 = pq.n) or what the journalled filters keep
+// (n0 = the rows they read).  false: filters ran and the survivors cannot be re-derived.  Caller holds the device's DeferLock.
+bool queue_survivors(int device, const PendingQueue &pq, const FilterJournal **journal, int *n0) {
+  *journal = nullptr;
+  *n0 = pq.n;
+  if (!pq.idx) return true;
+  auto j = t_state->journals.find(pq.idx);
+  if (j == t_state->journals.end() || !j->second.valid || j->second.start != 0 || j->second.device != device) return false;
+  *journal = &j->second;
+  *n0 = j->second.n0;
+  return true;
+}
+// every source column holds the n0 rows a scan reads
+bool columns_cover(const uint32_t *colRows, size_t count, int n0) {
+  for (size_t k = 0; k < count; k++)
+    if (colRows[k] < static_cast<uint32_t>(n0)) return false;
+  return true;
+}
+// The (zeroed) plan of a matched queue: its dimensions, its measure job — or, measureJob < 0, the constant measure of
+// Sort + Reduce — and the journal's filters.  false: the filters do not fit.  Caller holds the device's DeferLock.
+bool plan_from_queue(FusedPlanD &plan, const PendingQueue &pq, const DimLayoutD &L, const int (&dimJob)[kFusedDims], int measureJob, int valueBytes,
+                     uint64_t constBits, int constDtype, const FilterJournal *journal, int n0) {
+  const int nd = L.numDims;
+  for (int c = 0; c < nd; c++) fused_plan_dim(plan, c, pq.jobs.f[dimJob[c]], pq.jobs.s[dimJob[c]], L.width[c]);
+  if (measureJob >= 0) fused_plan_measure(plan, nd, pq.jobs.f[measureJob], pq.jobs.s[measureJob], valueBytes);
+  else fused_plan_const_measure(plan, nd, constBits, constDtype, valueBytes);
+  return !journal || (columns_cover(journal->colRows.data(), journal->filters.size(), n0) &&
+                      fused_plan_filters(plan, journal->filters.data(), journal->filters.size()));
+}
+// A fused scan evaluates the queue instead of launching it: `q` takes it over.  Caller holds the device's DeferLock.
+void take_queue(PendingQueue &pq, PendingQueue &q) {
+  q = pq;  // taken out of the queue: nobody else launches it
+  pq.jobs.count = 0;
+  pq.reads.clear();
+  pq.writes.clear();
+  pq.keep.clear();  // (the copy holds the decoded columns from here on: left in place they piled up, two per batch, for the life
+                    // of the stream — 86 GB after 143 archive batches — and every later copy of the queue took the pile along)
+  pq.overWait = false;
+  if (q.idx) {  // (decoded columns only the filters read live as long as the consumed queue does: the scan is launched by the caller)
+    auto jk = t_state->journals.find(q.idx);
+    if (jk != t_state->journals.end()) q.keep.insert(q.keep.end(), jk->second.keep.begin(), jk->second.keep.end());
+    t_state->journals.erase(q.idx);
+  }
+}
+// Runs a fused attempt.  An exception it throws still means "declined" (-1: the caller runs the ordinary sequence), but what
+// it said is kept: a line in the ARES_RTC_TRACE file and, with ARES_HR_TRACE, on stderr.
+template <typename Attempt>
+int guarded_attempt(const char *what, Attempt &&attempt) {
+  try {
+    return attempt();
+  } catch (std::exception &e) {
+    const std::string line = std::string(what) + " threw, the call falls back: " + e.what();
+    slow_trace(line.c_str(), 0.0);
+    if (hr_trace_enabled()) fprintf(stderr, "%s\n", line.c_str());
+    return -1;
+  }
+}
+}  // namespace
+
+// HashReduce's first move: when the stream's pending queue is exactly "the dimension columns and the
+// measure of rows [prev, prev + n) of inputKeys / inputValues", evaluate it on the fly (the fused
+// scan of hash_reduce_lds.hip) instead of launching it.  Returns false when the call must take the
+// ordinary path (whatever was pending has been launched, in stream order).
+bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const DimensionVector &in, const uint8_t *inValues,
+                                   const DimensionVector &out, uint8_t *outValues, int valueBytes, int length, int aggFunc,
+                                   int *groups) {
+  if (!fuse_available()) return false;
+  const bool forcedGlobal = global_table_forced();
+  PendingQueue q;
+  FusedPlanD plan;
+  memset(&plan, 0, sizeof(plan));
+  int nd = 0, prev = 0, n0 = 0;
+  AggSpec a;
+  {
+    DeferLock lock(device);
+    auto it = t_state->pending.find({device, stream});
+    if (it == t_state->pending.end() || it->second.jobs.count == 0) return false;
+    PendingQueue &pq = it->second;
+    bool ok = !forcedGlobal;
+    // dimension slots of 4, 2 or 1 bytes, in the vector's (descending width) order
+    nd = in.NumDimsPerDimWidth[2] + in.NumDimsPerDimWidth[3] + in.NumDimsPerDimWidth[4];
+    for (int k = 0; k < NUM_DIM_WIDTH; k++)
+      ok = ok && (k >= 2 || in.NumDimsPerDimWidth[k] == 0) && out.NumDimsPerDimWidth[k] == in.NumDimsPerDimWidth[k];
+    ok = ok && nd >= 1 && nd <= kFusedDims;
+    DimLayoutD L;
+    memset(&L, 0, sizeof(L));
+    if (ok) L = make_dim_layout(in.NumDimsPerDimWidth);
+    prev = length - pq.n;
+    // every dimension column and the measure of rows [prev, prev + n) must be a pending sink
+    int dimJob[kFusedDims], measureJob = -1;
+    ok = ok && prev >= 0 && pq.n > 0 && match_jobs(pq, in, L, prev, dimJob, &measureJob) && measureJob >= 0 &&
+         measure_job_matches(pq.jobs.s[measureJob], inValues + static_cast<size_t>(valueBytes) * prev, valueBytes, aggFunc);
+    if (ok) {
+      try {
+        a = make_agg_spec(aggFunc, valueBytes);
+        ok = hash_reduce_lds_supported(a);
+      } catch (std::exception &) {
+        ok = false;
+      }
+    }
+    const FilterJournal *journal = nullptr;
+    ok = ok && queue_survivors(device, pq, &journal, &n0) && columns_cover(pq.colRows, pq.jobs.count, n0) &&
+         plan_from_queue(plan, pq, L, dimJob, measureJob, valueBytes, 0, 0, journal, n0);
+    // the precompiled generic scan holds nd + 2 column slots; a narrow plan only ever runs on generated kernels (kFusedCols)
+    ok = ok && (plan.numCols <= nd + 2 || fused_plan_narrow(plan, nd));
+    if (!ok) {  // the ordinary path: the pending work runs now, ahead of this call on the same stream
+      launch_queue(stream, pq, /*inOrder=*/true);
+      g_releaseHeld(device, hold_tag(stream));
+      return false;
+    }
+    take_queue(pq, q);
+  }
+  DimensionVector prevKeys = in;
+  const int result = fused_hash_reduce_run(device, plan, n0, prevKeys, inValues, prev, out, outValues, a, stream);
+  DeferLock lock(device);
+  if (result < 0) {  // a partition region overflowed, or the call was declined: materialise the inputs after all
+    launch_queue(stream, q, /*inOrder=*/true);
+    lock.unlock();
+    g_releaseHeld(device, hold_tag(stream));
+    return false;
+  }
+  t_state->limbo[{device, stream}] = q;  // launchable until the next batch begins (begin_batch)
+  *groups = result;
+  return true;
+}
+
+// ---- Sort + Reduce over pending transforms (sort_reduce_fused.hip) ---------------------------------------------------------
+namespace {
 bool same_vector(const DimensionVector &a, const DimensionVector &b) {
   return a.DimValues == b.DimValues && a.HashValues == b.HashValues && a.IndexVector == b.IndexVector && a.VectorCapacity == b.VectorCapacity &&
          memcmp(a.NumDimsPerDimWidth, b.NumDimsPerDimWidth, sizeof(a.NumDimsPerDimWidth)) == 0;
@@ -2390,12 +2349,10 @@ bool define_lazy_sort(int device, hipStream_t stream, const DimensionVector &key
   if (it == t_state->pending.end() || it->second.jobs.count == 0) return false;
   const PendingQueue &pq = it->second;
   const int prev = length - pq.n;
-  int dimJob[kFusedDims], measureJob = -1;
-  if (pq.n <= 0 || prev < 0 || !match_sort_jobs(pq, keys, L, prev, dimJob, &measureJob)) return false;
-  if (pq.idx) {  // the survivors must be re-derivable from the filter journal
-    auto j = t_state->journals.find(pq.idx);
-    if (j == t_state->journals.end() || !j->second.valid || j->second.start != 0 || j->second.device != device) return false;
-  }
+  int dimJob[kFusedDims], measureJob = -1, n0 = 0;
+  const FilterJournal *journal = nullptr;
+  if (pq.n <= 0 || prev < 0 || !match_jobs(pq, keys, L, prev, dimJob, &measureJob)) return false;
+  if (!queue_survivors(device, pq, &journal, &n0)) return false;  // the survivors must be re-derivable from the filter journal
   uint8_t *hv = reinterpret_cast<uint8_t *>(keys.HashValues);
   retire_fills(device, ByteRange{hv, hv + 8ull * static_cast<size_t>(length)}, false);
   PendingSort ps{};
@@ -2426,7 +2383,7 @@ bool vector_sort_layout(const DimensionVector &keys) { return sort_vector_layout
 }  // namespace
 
 bool lazy_vector_sort_candidate(int device, const DimensionVector &keys, int length) {
-  static const bool trace = getenv("ARES_HR_TRACE") != nullptr;  // diagnostics
+  const bool trace = hr_trace_enabled();  // diagnostics
   if (trace)
     fprintf(stderr, "lazy_vector_sort_candidate: rows %d fuse %d enabled %d switch %d layout %d capacity %d\n", length, fuse_available() ? 1 : 0,
             fused_sort_reduce_enabled() ? 1 : 0, vector_sort_enabled() ? 1 : 0, vector_sort_layout(keys) ? 1 : 0, keys.VectorCapacity);
@@ -2472,7 +2429,48 @@ bool define_lazy_sort_vectors(int device, hipStream_t stream, const DimensionVec
   return false;
 }
 
-// Reduce over a Sort defined that way.  Caller: fuse_pending_into_sort_reduce.
+// ---- Reduce over a lazily defined Sort: what the scan-fed and the vector-sourced attempt share ------------------------------
+// The outputs are about to be rewritten: lazy work that targets them is retired or dropped.  Rows [0, readRows) of the input
+// vectors are read by this call's kernels: whatever still only defines them is written (no flush: a scan-fed batch's own lazy
+// compaction must stay lazy); readRows == 0: no previous result, nothing is read.
+static void prepare_sort_reduce(int device, const DimensionVector &in, const uint8_t *inValues, const DimensionVector &out, uint8_t *outValues,
+                                int valueBytes, int length, int readRows) {
+  const size_t rowBytes = dim_row_bytes(in.NumDimsPerDimWidth);  // (the caller has checked: out's layout is in's)
+  retire_fills_for_write(device, outValues, static_cast<size_t>(valueBytes) * length);
+  retire_fills_for_write(device, out.IndexVector, 4ull * static_cast<size_t>(length));
+  grouped_note_write(device, out);
+  grouped_note_write(device, outValues, static_cast<size_t>(valueBytes) * length);
+  drop_skipped_outputs(device, out.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity), outValues, static_cast<size_t>(valueBytes) * length);
+  if (readRows <= 0) return;
+  launch_pending_writers(device, in.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity));
+  launch_pending_writers(device, inValues, static_cast<size_t>(valueBytes) * readRows);
+  materialize_fills_for_read(device, in.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity));
+  materialize_fills_for_read(device, inValues, static_cast<size_t>(valueBytes) * readRows);
+}
+// The kernels wrote `result` groups: the reduced state is entered; `consumed` (scan-fed only) is the queue the scan evaluated —
+// launchable until the next batch begins (begin_batch).  Returns true.
+static bool reduced_sort_done(int device, hipStream_t stream, const PendingSort &ps, const DimensionVector &in, uint8_t *inValues,
+                              const DimensionVector &out, uint8_t *outValues, int valueBytes, int length, int aggFunc, int result,
+                              const PendingQueue *consumed, int *groups) {
+  mem_note_dim_rows(device, out, 0, static_cast<size_t>(result));
+  mem_note_write(device, outValues, static_cast<size_t>(valueBytes) * static_cast<size_t>(result));
+  DeferLock lock(device);
+  if (consumed) t_state->limbo[{device, stream}] = *consumed;
+  enter_reduced_sort(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result);
+  *groups = result;
+  return true;
+}
+// The real thing: InitIndexVector, Sort (the ordinary Reduce follows).  Returns false.
+static bool sort_for_real(int device, hipStream_t stream, const DimensionVector &in, int length) {
+  {
+    DeferLock lock(device);
+    launch_init_index(in.IndexVector, 0, length, stream);
+  }
+  sort_keys_now(in, length, stream);
+  return false;
+}
+
+// Reduce over a Sort defined over materialised vectors.  Caller: fuse_pending_into_sort_reduce.
 static bool reduce_lazy_vector_sort(int device, hipStream_t stream, const DimensionVector &in, uint8_t *inValues, const DimensionVector &out,
                                     uint8_t *outValues, int valueBytes, int length, int aggFunc, int *groups) {
   PendingSort ps{};
@@ -2499,38 +2497,11 @@ static bool reduce_lazy_vector_sort(int device, hipStream_t stream, const Dimens
     }
     drop_sort(in.IndexVector);  // (while the kernels run nothing is defined; the reduced state is entered below)
   }
-  size_t rowBytes = 0;
-  for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(in.NumDimsPerDimWidth[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
-  retire_fills_for_write(device, outValues, static_cast<size_t>(valueBytes) * length);
-  retire_fills_for_write(device, out.IndexVector, 4ull * static_cast<size_t>(length));
-  grouped_note_write(device, out);
-  grouped_note_write(device, outValues, static_cast<size_t>(valueBytes) * length);
-  drop_skipped_outputs(device, out.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity), outValues, static_cast<size_t>(valueBytes) * length);
-  // every row is read by this call's kernels: whatever still only defines one is written
-  launch_pending_writers(device, in.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity));
-  launch_pending_writers(device, inValues, static_cast<size_t>(valueBytes) * length);
-  materialize_fills_for_read(device, in.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity));
-  materialize_fills_for_read(device, inValues, static_cast<size_t>(valueBytes) * length);
-  int result;
-  try {
-    result = fused_sort_reduce_vectors(device, length, in, inValues, out, outValues, a, stream);
-  } catch (...) {
-    result = -1;
-  }
-  if (result < 0) {  // declined (a kernel still being compiled, too many rows), or a table overflowed: the real thing
-    {
-      DeferLock lock(device);
-      launch_init_index(in.IndexVector, 0, length, stream);
-    }
-    sort_keys_now(in, length, stream);
-    return false;
-  }
-  mem_note_dim_rows(device, out, 0, static_cast<size_t>(result));
-  mem_note_write(device, outValues, static_cast<size_t>(valueBytes) * static_cast<size_t>(result));
-  DeferLock lock(device);
-  enter_reduced_sort(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result);
-  *groups = result;
-  return true;
+  // every row is read by this call's kernels
+  prepare_sort_reduce(device, in, inValues, out, outValues, valueBytes, length, /*readRows=*/length);
+  const int result = guarded_attempt("fused_sort_reduce_vectors", [&] { return fused_sort_reduce_vectors(device, length, in, inValues, out, outValues, a, stream); });
+  if (result < 0) return sort_for_real(device, stream, in, length);  // declined (a kernel still being compiled, too many rows), or a table overflowed
+  return reduced_sort_done(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result, nullptr, groups);
 }
 
 bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const DimensionVector &in, uint8_t *inValues, const DimensionVector &out,
@@ -2572,7 +2543,7 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
     int dimJob[kFusedDims], measureJob = -1;
     if (ok) {
       prev = length - it->second.n;
-      ok = it->second.n > 0 && prev >= 0 && match_sort_jobs(it->second, in, L, prev, dimJob, &measureJob);
+      ok = it->second.n > 0 && prev >= 0 && match_jobs(it->second, in, L, prev, dimJob, &measureJob);
     }
     if (ok) {
       try {
@@ -2583,26 +2554,13 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
       }
     }
     const FilterJournal *journal = nullptr;
+    ok = ok && queue_survivors(device, it->second, &journal, &n0) && columns_cover(it->second.colRows, it->second.jobs.count, n0);
     if (ok) {
       const PendingQueue &pq = it->second;
-      n0 = pq.n;
-      if (pq.idx) {
-        auto j = t_state->journals.find(pq.idx);
-        ok = j != t_state->journals.end() && j->second.valid && j->second.start == 0 && j->second.device == device;
-        if (ok) {
-          journal = &j->second;
-          n0 = journal->n0;
-        }
-      }
-    }
-    if (ok) {
-      const PendingQueue &pq = it->second;
-      for (int k = 0; ok && k < pq.jobs.count; k++) ok = pq.colRows[k] >= static_cast<uint32_t>(n0);
       uint8_t *measureRows = inValues + static_cast<size_t>(valueBytes) * prev;
-      if (ok && measureJob >= 0) {
-        const SinkD &sm = pq.jobs.s[measureJob];
-        ok = sm.values == measureRows && sm.width == valueBytes && sm.agg == aggFunc && !(valueBytes == 8 && sm.identity != 0);
-      } else if (ok) {  // a constant measure (COUNT(*)): the rows are a lazy fill
+      if (measureJob >= 0) {
+        ok = measure_job_matches(pq.jobs.s[measureJob], measureRows, valueBytes, aggFunc);
+      } else {  // a constant measure (COUNT(*)): the rows are a lazy fill
         auto f = t_state->fills.find(measureRows);
         ok = f != t_state->fills.end() && f->second.device == device && !f->second.sortIdx && f->second.unit == valueBytes &&
              f->second.bytes == static_cast<size_t>(valueBytes) * pq.n;
@@ -2613,106 +2571,22 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
           constBits = fill.pattern;
         }
       }
-    }
-    if (ok) {
-      const PendingQueue &pq = it->second;
-      auto column_of = [](const FastOperands &f) { return FusedColumn{f.vals, f.nulls, f.bitOff, static_cast<uint32_t>(f.step ? f.step : 4)}; };
-      auto strip = [](FastOperands f) {
-        f.vals = nullptr;
-        f.nulls = nullptr;
-        f.idx = nullptr;
-        f.pad = 0;
-        return f;
-      };
-      auto kind_of = [](int dtype) { return (dtype == Int32 || dtype == Int16 || dtype == Int8) ? K_I32 : (dtype == Uint32 || dtype == Uint16 || dtype == Uint8) ? K_U32 : K_F32; };
-      for (int c = 0; c < nd; c++) {
-        const int k = dimJob[c];
-        plan.cols[c] = column_of(pq.jobs.f[k]);
-        plan.dims[c].f = strip(pq.jobs.f[k]);
-        plan.dims[c].col = c;
-        plan.dims[c].outKind = kind_of(pq.jobs.s[k].dtype);
-        plan.dimWidth[c] = L.width[c];
-      }
-      plan.numCols = nd;
-      plan.measureWidth = valueBytes;
-      if (measureJob >= 0) {
-        plan.cols[nd] = column_of(pq.jobs.f[measureJob]);
-        plan.measure.f = strip(pq.jobs.f[measureJob]);
-        plan.measure.col = nd;
-        plan.measure.outKind = kind_of(pq.jobs.s[measureJob].dtype);
-        plan.measureDtype = pq.jobs.s[measureJob].dtype;
-        plan.identity = pq.jobs.s[measureJob].identity;
-        plan.numCols = nd + 1;
-      } else {
-        plan.measure.col = -1;
-        plan.measure.f.bbits = static_cast<uint32_t>(constBits);  // (what the scan's records carry; the merge takes constBits)
-        plan.measureDtype = valueBytes == 8 ? Int64 : (a.vtype == V_I32 ? Int32 : Uint32);
-      }
-      if (journal) {
-        ok = journal->filters.size() <= static_cast<size_t>(kFusedFilters);
-        for (size_t k = 0; ok && k < journal->filters.size(); k++) {
-          const FastOperands &f = journal->filters[k];
-          ok = journal->colRows[k] >= static_cast<uint32_t>(n0);
-          int col = -1;
-          for (int c = 0; c < plan.numCols; c++)
-            if (plan.cols[c].vals == f.vals && plan.cols[c].nulls == f.nulls && plan.cols[c].bitOff == f.bitOff &&
-                plan.cols[c].step == static_cast<uint32_t>(f.step ? f.step : 4))
-              col = c;
-          if (col < 0 && plan.numCols < kFusedCols) {
-            col = plan.numCols++;
-            plan.cols[col] = column_of(f);
-          }
-          ok = ok && col >= 0;
-          plan.filters[k].f = strip(f);
-          plan.filters[k].col = col;
-          plan.filters[k].outKind = K_BOOL;
-        }
-        plan.numFilters = static_cast<int>(journal->filters.size());
-      }
+      ok = ok && plan_from_queue(plan, pq, L, dimJob, measureJob, valueBytes, constBits, valueBytes == 8 ? Int64 : (a.vtype == V_I32 ? Int32 : Uint32),
+                                 journal, n0);
     }
     if (!ok) {  // not this case after all: Sort runs (and the ordinary Reduce follows)
       materialize_sort(in.IndexVector);
       return false;
     }
-    PendingQueue &pq = it->second;
-    q = pq;  // taken out of the queue: nobody else launches it
-    pq.jobs.count = 0;
-    pq.reads.clear();
-    pq.writes.clear();
-    pq.keep.clear();  // (the copy holds the decoded columns from here on: left in place they piled up, two per batch, for the life
-                      // of the stream — 86 GB after 143 archive batches — and every later copy of the queue took the pile along)
-    pq.overWait = false;
-    if (q.idx) {  // (decoded columns only the filters read live as long as the consumed queue does: the scan is launched below)
-      auto jk = t_state->journals.find(q.idx);
-      if (jk != t_state->journals.end()) q.keep.insert(q.keep.end(), jk->second.keep.begin(), jk->second.keep.end());
-      t_state->journals.erase(q.idx);
-    }
+    take_queue(it->second, q);
     if (constMeasure) t_state->fills.erase(fillAt);
     drop_sort(in.IndexVector);  // (while the kernels run nothing is defined; the reduced state is entered below)
   }
-  // the outputs are about to be rewritten, the previous result is read by kernels of this call
-  retire_fills_for_write(device, outValues, static_cast<size_t>(valueBytes) * length);
-  retire_fills_for_write(device, out.IndexVector, 4ull * static_cast<size_t>(length));
-  grouped_note_write(device, out);
-  grouped_note_write(device, outValues, static_cast<size_t>(valueBytes) * length);
-  {
-    size_t rowBytes = 0;
-    for (int w = 0; w < NUM_DIM_WIDTH; w++) rowBytes += static_cast<size_t>(out.NumDimsPerDimWidth[w]) * ((1u << (NUM_DIM_WIDTH - 1 - w)) + 1);
-    drop_skipped_outputs(device, out.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity), outValues, static_cast<size_t>(valueBytes) * length);
-    if (prev > 0) {  // rows [0, prev) are read by this call's kernels: whatever still only defines them is written (no flush:
-                     // this batch's own lazy compaction must stay lazy)
-      launch_pending_writers(device, in.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity));
-      launch_pending_writers(device, inValues, static_cast<size_t>(valueBytes) * prev);
-      materialize_fills_for_read(device, in.DimValues, rowBytes * static_cast<size_t>(in.VectorCapacity));
-      materialize_fills_for_read(device, inValues, static_cast<size_t>(valueBytes) * prev);
-    }
-  }
-  int result;
-  try {
-    result = fused_sort_reduce_run(device, plan, nd, constMeasure, constBits, n0, in, inValues, prev, out, outValues, a, stream);
-  } catch (...) {
-    result = -1;
-  }
+  // the previous result — rows [0, prev) — is read by kernels of this call
+  prepare_sort_reduce(device, in, inValues, out, outValues, valueBytes, length, /*readRows=*/prev);
+  const int result = guarded_attempt("fused_sort_reduce_run", [&] {
+    return fused_sort_reduce_run(device, plan, nd, constMeasure, constBits, n0, in, inValues, prev, out, outValues, a, stream);
+  });
   if (result < 0) {  // declined, or a partition overflowed: the batch's rows are written — transforms, the constant rows — ...
     {
       DeferLock lock(device);
@@ -2723,41 +2597,19 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
     // ... and the groups are ordered by row hash over the rows that exist now (the wide layout takes results the 512 tables
     // of the scan-fed path do not: millions of groups per batch) ...
     int wide = kFusedUnavailable;
-    if (vector_sort_enabled() && vector_sort_layout(in)) {
-      try {
-        wide = fused_sort_reduce_vectors(device, length, in, inValues, out, outValues, a, stream);
-      } catch (...) {
-        wide = -1;
-      }
-    }
+    if (vector_sort_enabled() && vector_sort_layout(in))
+      wide = guarded_attempt("fused_sort_reduce_vectors", [&] { return fused_sort_reduce_vectors(device, length, in, inValues, out, outValues, a, stream); });
     if (wide >= 0) {
-      mem_note_dim_rows(device, out, 0, static_cast<size_t>(wide));
-      mem_note_write(device, outValues, static_cast<size_t>(valueBytes) * static_cast<size_t>(wide));
-      DeferLock lock(device);
       ps.fromVectors = true;
-      enter_reduced_sort(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, wide);
-      *groups = wide;
-      return true;
+      return reduced_sort_done(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, wide, nullptr, groups);
     }
-    // ... or the real thing: InitIndexVector, Sort (the ordinary Reduce follows)
-    {
-      DeferLock lock(device);
-      launch_init_index(in.IndexVector, 0, length, stream);
-    }
-    sort_keys_now(in, length, stream);
-    return false;
+    return sort_for_real(device, stream, in, length);  // ... or the real thing
   }
-  mem_note_dim_rows(device, out, 0, static_cast<size_t>(result));
-  mem_note_write(device, outValues, static_cast<size_t>(valueBytes) * static_cast<size_t>(result));
-  DeferLock lock(device);
   q.sortIdx = in.IndexVector;
-  t_state->limbo[{device, stream}] = q;  // launchable until the next batch begins (begin_batch)
   ps.constMeasure = constMeasure;
   ps.fill = fill;
   ps.fillAt = fillAt;
-  enter_reduced_sort(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result);
-  *groups = result;
-  return true;
+  return reduced_sort_done(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result, &q, groups);
 }
 
 // tile counts of an existing predicate vector, in filter_pred_kernel's tile geometry
