@@ -126,12 +126,21 @@ std::string const_name(int slot) { return "a.k[" + std::to_string(slot) + "]"; }
 // value expression of one element: writes `r` (result bits) given `v` (stored bits) and `okb` (0/1);
 // `kc` names the run-time constant of the expression.  Returns false when the shape is outside the fast
 // paths of eval_quad.
-bool gen_value(const FastOperands &f, std::ostringstream &o, const char *v, const char *okb, const char *r, const std::string &kc) {
+// floatArith (the Sort + Reduce scan's measure only): a float column combined with a float constant by Plus / Minus /
+// Multiply (fare * 1.5) — binary32's float branch: one rounding, null -> bits 0.
+bool gen_value(const FastOperands &f, std::ostringstream &o, const char *v, const char *okb, const char *r, const std::string &kc,
+               bool floatArith = false) {
   if (!col_kind(f.akind)) return false;
   const bool intKinds = f.akind != K_F32 && f.I != K_F32 && f.akind != K_BOOL;
   if (f.arity == 1) {
     if (!(f.akind == f.I || intKinds)) return false;
     o << "      " << r << " = " << v << ";\n";  // a null bare column keeps its stored bits (functor.hpp:345-351)
+    return true;
+  }
+  if (floatArith && f.arity == 2 && f.akind == K_F32 && f.I == K_F32 && f.bkind == K_F32 && f.rk == K_F32 && f.bok && !f.divLike &&
+      (f.functor == Plus || f.functor == Minus || f.functor == Multiply)) {
+    o << "      " << r << " = " << okb << " ? __float_as_uint(__uint_as_float(" << v << ")"
+      << (f.functor == Plus ? " + " : f.functor == Minus ? " - " : " * ") << "__uint_as_float(" << kc << ")) : 0u;\n";
     return true;
   }
   if (f.arity != 2 || !intKinds || !int_kind(f.I) || !int_kind(f.bkind) || !f.bok) return false;
@@ -957,7 +966,7 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
       if (e.col != nd) return "";
       o << "#pragma unroll\n  for (int j = 0; j < 4; j++) {\n"
            "    const u32 v = r.v[" << nd << "][j]; const u32 okb = (okc[" << nd << "] >> j) & 1u; u32 x;\n";
-      if (!gen_value(e.f, o, "v", "okb", "x", const_name(const_slot_measure()))) return "";
+      if (!gen_value(e.f, o, "v", "okb", "x", const_name(const_slot_measure()), sort64)) return "";
       if (plan.measureWidth == 8) {
         if (plan.identity != 0) return "";
         o << "    cv[j] = okb ? x : 0u;\n";

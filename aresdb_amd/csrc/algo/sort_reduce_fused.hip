@@ -9,7 +9,8 @@
 // What a caller can observe of Sort + Reduce over rows [0, prev) (the previous result) + [prev, prev + n) (the batch):
 //   * the output groups in ASCENDING order of the 64-bit row hash, one group per distinct hash;
 //   * each group's dimension row = that of its lowest-indexed row (stable sort of an iota index vector);
-//   * each group's value = op over its rows' values (integer aggregates: independent of the order).
+//   * each group's value = op over its rows' values (integer aggregates, float MIN / MAX: independent of the order; float
+//     sums and averages: within the tolerance the project grants them everywhere — INTEGRATION.md).
 // Sorting 40-60 M surviving ROWS per batch to find 70 k - 2 M groups is what made this path 6-7 x slower than HashReduce
 // (4 radix passes + hash + reduce + compaction + materialised dimension rows: 4.4 ms per 64 Mi-row batch).  Here the
 // GROUPS are ordered instead:
@@ -25,8 +26,12 @@
 //                          entry = occupied slots before its cluster + keys of the cluster below its own — no sort pass;
 //   4. sr_emit_kernel      prefix over the partitions' group counts, dimension rows of the representatives gathered (previous
 //                          result) or re-evaluated from the source columns (batch rows), values stored: ascending hash order.
-// Float sums keep the real sort (their order of additions is observable), as does anything this path declines: more
-// groups than the partitions' tables hold, a skewed partition stream, a record whose hash equals the table's "empty" word.
+// Float aggregates ride the same tables: SUM_FLOAT into 8 or 4 bytes, MIN_FLOAT, MAX_FLOAT (one LDS instruction per record,
+// like the integer ones) on both layouts, AVG_FLOAT (a compare-and-swap loop) on the wide one.  Their additions land in
+// whatever order the records arrive in: group count, order, representatives, dimension bytes, AVG's counts, MIN / MAX stay
+// bit-exact, a sum's last bits may differ from run to run — ARES_SR_FLOAT=0 gives the sorted order back (the real sort).
+// The real sort also takes anything this path declines: more groups than the partitions' tables hold, a skewed partition
+// stream, a record whose hash equals the table's "empty" word, a NaN among MIN_FLOAT / MAX_FLOAT values.
 //
 // The same over rows that EXIST (a joined column, a generic expression, an eager host — or what the scan-fed path above
 // declined, after its transforms were launched): fused_sort_reduce_vectors at the end of this file, the "wide layout" —
@@ -165,9 +170,21 @@ struct Slots {
   using V = typename std::conditional<VW == 4, uint32_t, uint64_t>::type;
 };
 
-template <int VW>
+// FLT: the slot holds a float aggregate — SUM_FLOAT into 8 bytes (V_F64) or 4 (V_F32), MIN_FLOAT / MAX_FLOAT (V_F32), or
+// AVG_FLOAT's packed {f32 average, u32 count} (V_AVG).  Sums and MIN / MAX are one LDS instruction each (ds_add_f64, ds_add_f32,
+// ds_min_f32, ds_max_f32), like their integer siblings; the integer instantiations (FLT = false) are what they were.
+template <int VW, bool FLT>
 __device__ __forceinline__ void sr_aggregate(typename Slots<VW>::V *slot, uint64_t bits, const AggSpec &a) {
-  if constexpr (VW == 8) {
+  if constexpr (FLT && VW == 8) {
+    __hip_atomic_fetch_add(reinterpret_cast<double *>(slot), __longlong_as_double(static_cast<long long>(bits)), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else if constexpr (FLT) {
+    float *pf = reinterpret_cast<float *>(slot);
+    const float x = bits_f(static_cast<uint32_t>(bits));
+    if (a.op == OP_SUM) __hip_atomic_fetch_add(pf, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else if (a.op == OP_MIN) __hip_atomic_fetch_min(pf, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    else __hip_atomic_fetch_max(pf, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else if constexpr (VW == 8) {
     __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(slot), static_cast<unsigned long long>(bits), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_WORKGROUP);
   } else {
@@ -185,8 +202,29 @@ __device__ __forceinline__ void sr_aggregate(typename Slots<VW>::V *slot, uint64
     }
   }
 }
+// AVG_FLOAT: RollingAvgFunctor has no LDS instruction — a compare-and-swap loop on the group's slot.  A sequential reduce
+// STARTS from a group's first value (rolling_avg(identity, x) = x / c * c is not always x): a slot whose count is still 0
+// takes the record as it is.  Only ever aimed at a record's own slot: many lanes looping on the spare slot would serialise.
+__device__ __forceinline__ void sr_average(uint64_t *slot, uint64_t x) {
+  unsigned long long *p = reinterpret_cast<unsigned long long *>(slot);
+  unsigned long long old = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  for (;;) {
+    const unsigned long long next = (old >> 32) == 0 ? x : rolling_avg(old, x);
+    if (__hip_atomic_compare_exchange_strong(p, &old, next, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) break;
+  }
+}
+// MIN_FLOAT / MAX_FLOAT over a NaN: the reference's functor (q < p ? q : p over the rows in sorted order) lets a NaN win only
+// where it comes first, ds_min_f32 / ds_max_f32 drop it (IEEE minNum / maxNum) — such a call takes the real sort
+template <int VW, bool FLT>
+__device__ __forceinline__ bool sr_unordered(uint64_t bits, const AggSpec &a) {
+  if constexpr (FLT && VW == 4) {
+    const float x = bits_f(static_cast<uint32_t>(bits));
+    return a.op != OP_SUM && x != x;
+  }
+  return false;
+}
 
-template <int VW, bool WIDE>
+template <int VW, bool WIDE, bool FLT>
 __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrArgs m) {
   using T = Table<VW, WIDE>;
   using V = typename Slots<VW>::V;
@@ -286,9 +324,18 @@ __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrA
     }
     return -1;
   };
+  // (AVG_FLOAT reaches the wide layout only: its measure is never carried by a scan-fed record)
+  const bool average = FLT && WIDE && VW == 8 && a.vtype == V_AVG;
   auto settle = [&](int slot, uint32_t row, uint64_t value) {
     __hip_atomic_fetch_min(sRows + slot, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    sr_aggregate<VW>(sVals + slot, value, a);
+    if constexpr (FLT && WIDE && VW == 8) {
+      if (average) {
+        sr_average(reinterpret_cast<uint64_t *>(sVals + slot), value);
+        return;
+      }
+    }
+    if (sr_unordered<VW, FLT>(value, a)) m.flags[2] = 1u;  // (a NaN among MIN / MAX values: the caller takes the real sort)
+    sr_aggregate<VW, FLT>(sVals + slot, value, a);
   };
   auto insert = [&](uint32_t row, uint32_t hi, uint32_t lo, uint64_t value) {  // the general loop, one record
     if ((hi & lo) == 0xFFFFFFFFu) {  // the table's empty word: the caller takes the real sort
@@ -409,7 +456,16 @@ __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrA
         const uint64_t value = m.constMeasure ? m.constBits : (WIDE && m.gatherValues) ? (valid ? load_value_bits(m.inValues, a, r[k].x) : 0ull) : hr::widen_value(m.widen, r[k].z);
         // (the group's lowest row is settled after its first few records: a plain read tells the rest they need no atomic)
         if (hit && r[k].x < sRows[slot]) __hip_atomic_fetch_min(sRows + slot, r[k].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        sr_aggregate<VW>(sVals + slot, hit ? value : a.identity, a);
+        if constexpr (FLT && WIDE && VW == 8) {
+          if (average) {
+            if (hit) sr_average(reinterpret_cast<uint64_t *>(sVals + slot), value);
+          } else {
+            sr_aggregate<VW, FLT>(sVals + slot, hit ? value : a.identity, a);
+          }
+        } else {
+          if (hit && sr_unordered<VW, FLT>(value, a)) m.flags[2] = 1u;
+          sr_aggregate<VW, FLT>(sVals + slot, hit ? value : a.identity, a);
+        }
         pend |= (valid && !hit ? 1u : 0u) << k;
       }
       // Records that did not meet their group at home (it lives further on, or is new: a few lanes per segment) are queued
@@ -705,7 +761,7 @@ __global__ __launch_bounds__(256) void sr_bounds_kernel(const uint64_t *prevKeys
 // (level-1 partition, group of streams), twice: sr_count_kernel adds its records per partition (LDS histogram, one global
 // atomic per partition it meets); after the prefix over the counts sr_split_kernel reserves its share of each run with one
 // atomic per partition and writes the records there.  Order within a partition does not matter to the merge (lowest row by atomic
-// min, integer aggregates).
+// min; integer aggregates and float MIN / MAX commute, float sums hold a tolerance).
 struct SplitArgs {
   const uint4 *rec1;
   const uint32_t *counts1;
@@ -1033,15 +1089,29 @@ bool fused_sort_reduce_enabled() {
   return on.get() && rtc_scan_available();
 }
 
+namespace {
+bool float_agg(const AggSpec &a) { return a.vtype == V_F32 || a.vtype == V_F64 || a.vtype == V_AVG; }
+// ARES_SR_FLOAT=0: float aggregates keep the real sort — their additions then run in the sorted order (ascending hash, then
+// row), the same bits every time; on this path a float sum's (an average's) last bits depend on the order the LDS adds landed in
+bool float_aggregates_enabled() {
+  static EnvSwitch<bool> on("ARES_SR_FLOAT", [](const char *e) { return !(e && e[0] == '0'); });
+  return on.get();
+}
+}  // namespace
+
 bool fused_sort_reduce_supported(const AggSpec &a) {
   if (a.vtype == V_U32 || a.vtype == V_I32) return a.op == OP_SUM || a.op == OP_MIN || a.op == OP_MAX;
-  return (a.vtype == V_U64 || a.vtype == V_I64) && a.op == OP_SUM;
+  if (a.vtype == V_U64 || a.vtype == V_I64) return a.op == OP_SUM;
+  if (!float_aggregates_enabled()) return false;
+  if (a.vtype == V_F32) return a.op == OP_SUM || a.op == OP_MIN || a.op == OP_MAX;
+  return (a.vtype == V_F64 && a.op == OP_SUM) || (a.vtype == V_AVG && a.op == OP_AVG);  // (AVG_FLOAT: the wide layout only)
 }
 
 int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool constMeasure, uint64_t constBits, int batchRows,
                           const DimensionVector &in, const uint8_t *inValues, int prevSize, const DimensionVector &out,
                           uint8_t *outValues, const AggSpec &a, hipStream_t stream) {
   if (!fused_sort_reduce_enabled() || !fused_sort_reduce_supported(a) || batchRows <= 0 || prevSize < 0) return kFusedUnavailable;
+  if (a.vtype == V_AVG) return kFusedUnavailable;  // (a record carries 4 bytes: no room for {average, count})
   // ARES_SR_SCAN_FED=0 (tests): this path declines everything — its callers go on to the wide layout over materialised rows
   static EnvSwitch<bool> scanFed("ARES_SR_SCAN_FED", [](const char *e) { return !(e && e[0] == '0'); });
   if (!scanFed.get()) return kFusedUnavailable;
@@ -1130,11 +1200,14 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
   }
   rtc_sort_scan_launch(scan, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
   m.phases = merge_phase_stamps(numParts, stream);
+  const bool flt = float_agg(a);
   if (vw == 8) {
-    ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false>), numParts, kThreads, stream, m);
+    if (flt) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false, true>), numParts, kThreads, stream, m);
+    else ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false, false>), numParts, kThreads, stream, m);
     ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<8, false>), numParts, kThreads, stream, m, plan, L);
   } else {
-    ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<4, false>), numParts, kThreads, stream, m);
+    if (flt) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<4, false, true>), numParts, kThreads, stream, m);
+    else ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<4, false, false>), numParts, kThreads, stream, m);
     ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<4, false>), numParts, kThreads, stream, m, plan, L);
   }
   uint32_t w[3] = {0, 0, 0};
@@ -1167,7 +1240,8 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
 //                      out in the order they lie in).
 // Up to eight dimensions in slots of 16 / 8 / 4 / 2 / 1 bytes (sort_vector_layout_supported: the scan is the one kernel that
 // reads the rows by slot width — the split and the merge see 64-bit hashes, the emit copies rows with copy_dim_row) and
-// integer aggregates of 4 or 8 bytes; returns like fused_sort_reduce_run.
+// aggregates of 4 or 8 bytes (fused_sort_reduce_supported: AVG_FLOAT's {average, count} pairs included — gathered by row like
+// every 8-byte value); returns like fused_sort_reduce_run.
 static int sort_reduce_vectors_run(int device, int length, const DimensionVector &in, const uint8_t *inValues, const DimensionVector &out,
                                    uint8_t *outValues, const AggSpec &a, hipStream_t stream, int slack, bool spread) {
   const bool trace = hr_trace_enabled();  // diagnostics
@@ -1251,10 +1325,10 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
   m.inValues = inValues;
   m.inCapacity = static_cast<size_t>(in.VectorCapacity);
   m.prevSize = static_cast<uint32_t>(prevSize);
-  m.widen.mode = 0;
-  m.widen.rk = a.vtype == V_I32 ? K_I32 : K_U32;
-  m.widen.dtype = a.vtype == V_I32 ? Int32 : Uint32;
-  m.gatherValues = vw == 8 ? 1 : 0;
+  m.widen.mode = 0;  // (a record's 4 bytes ARE the value, whatever its kind: nothing is widened)
+  m.widen.rk = a.vtype == V_F32 ? K_F32 : a.vtype == V_I32 ? K_I32 : K_U32;
+  m.widen.dtype = a.vtype == V_F32 ? Float32 : a.vtype == V_I32 ? Int32 : Uint32;
+  m.gatherValues = vw == 8 ? 1 : 0;  // (8-byte sums of either kind, AVG_FLOAT's pairs)
   m.agg = a;
   m.staging = reinterpret_cast<uint4 *>(shared);
   m.stageKeys = reinterpret_cast<uint64_t *>(shared + stageBytes);
@@ -1310,8 +1384,11 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
   m.phases = merge_phase_stamps(numParts, stream);
   FusedPlanD noPlan;
   memset(&noPlan, 0, sizeof(noPlan));
-  if (vw == 8) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, true>), numParts, T::kLanes, stream, m);
-  else ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<4, true>), numParts, T::kLanes, stream, m);
+  const bool flt = float_agg(a);
+  if (vw == 8 && flt) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, true, true>), numParts, T::kLanes, stream, m);
+  else if (vw == 8) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, true, false>), numParts, T::kLanes, stream, m);
+  else if (flt) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<4, true, true>), numParts, T::kLanes, stream, m);
+  else ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<4, true, false>), numParts, T::kLanes, stream, m);
   ARES_LAUNCH("sr_prefix_kernel", sr_prefix_kernel, 1, 1024, stream, partCount, numParts, partBase, flags);  // (flags[0]: groups)
   if (vw == 8) ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<8, true>), numParts, T::kLanes, stream, m, noPlan, L);
   else ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<4, true>), numParts, T::kLanes, stream, m, noPlan, L);

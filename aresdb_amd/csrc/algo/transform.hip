@@ -2571,8 +2571,8 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
           constBits = fill.pattern;
         }
       }
-      ok = ok && plan_from_queue(plan, pq, L, dimJob, measureJob, valueBytes, constBits, valueBytes == 8 ? Int64 : (a.vtype == V_I32 ? Int32 : Uint32),
-                                 journal, n0);
+      const int constDtype = a.vtype == V_F64 ? Float64 : a.vtype == V_F32 ? Float32 : valueBytes == 8 ? Int64 : (a.vtype == V_I32 ? Int32 : Uint32);
+      ok = ok && plan_from_queue(plan, pq, L, dimJob, measureJob, valueBytes, constBits, constDtype, journal, n0);
     }
     if (!ok) {  // not this case after all: Sort runs (and the ordinary Reduce follows)
       materialize_sort(in.IndexVector);

@@ -129,10 +129,11 @@ def _zipf_cdf(alpha, k, device):
     return (torch.cumsum(w, 0) / w.sum()).to(torch.float32)
 
 
-def c3_batch(n, gen: torch.Generator, device, null_fraction=0.01) -> Dict[str, ResidentColumn]:
+def c3_batch(n, gen: torch.Generator, device, null_fraction=0.01, quantised=True) -> Dict[str, ResidentColumn]:
     """One batch of BASELINE config C3: ts uniform over 7 days, d1 uniform [0,100),
     d2 Zipf(1.1) over [0,50), d3 uniform [0,2), m float32 uniform [0,100) (quarter steps so float64
-    sums are exact in any order)."""
+    sums are exact in any order; quantised=False: full mantissas — sums then depend on the order of
+    additions in their last bits, what the float tolerance of aresdb_amd/check.py is for)."""
     def ri(hi):
         return torch.randint(0, hi, (n,), dtype=torch.int32, device=device, generator=gen)
     cols = {"ts": ri(86400 * 7), "d1": ri(100)}
@@ -140,7 +141,10 @@ def c3_batch(n, gen: torch.Generator, device, null_fraction=0.01) -> Dict[str, R
     cols["d2"] = torch.searchsorted(_zipf_cdf(1.1, 50, device), u).clamp_(max=49).to(torch.int32)
     del u
     cols["d3"] = ri(2)
-    cols["m"] = ri(400).to(torch.float32) * 0.25
+    if quantised:
+        cols["m"] = ri(400).to(torch.float32) * 0.25
+    else:
+        cols["m"] = torch.rand((n,), dtype=torch.float32, device=device, generator=gen) * 100.0
     out = {}
     for name, dt in C3_COLUMNS:
         valid = None
@@ -178,14 +182,17 @@ def c3_archive_batch(n, gen: torch.Generator, device, null_fraction=0.01) -> Dic
     return out
 
 
-def c3_shard(rows, batch_rows, seed, device, null_fraction=0.01, archive=False) -> List[Dict[str, ResidentColumn]]:
+def c3_shard(rows, batch_rows, seed, device, null_fraction=0.01, archive=False, quantised=True) -> List[Dict[str, ResidentColumn]]:
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     batches = []
     done = 0
     while done < rows:
         n = min(batch_rows, rows - done)
-        batches.append((c3_archive_batch if archive else c3_batch)(n, gen, device, null_fraction))
+        if archive:
+            batches.append(c3_archive_batch(n, gen, device, null_fraction))
+        else:
+            batches.append(c3_batch(n, gen, device, null_fraction, quantised))
         done += n
     return batches
 

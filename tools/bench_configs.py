@@ -361,6 +361,52 @@ def wide_key_legs(be, dev, which, rows, batch_rows=1 << 26, steps=3):
              "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}]
 
 
+def sort_float_leg(be, dev, rows, batch_rows=1 << 26, steps=3):
+    """c3sortfloat: the headline query under the reference's SHIPPED configuration (enable_hash_reduction: false): SUM(m) of a
+    Float32 column into float64 through Sort + Reduce, `rows` rows as 64 Mi-row batches resident in HBM, a measure column of
+    full-mantissa floats (workload.c3_shard(quantised=False)).  Float aggregates order GROUPS in LDS tables
+    (sort_reduce_fused.hip); ARES_SR_FLOAT=0 in the environment gives the same leg on the real row sort.  Every key's sum is
+    compared at rel = 1e-6 with the exact group-by of aresdb_amd/check.py and the rows must come in ascending order of their
+    64-bit row hash.  ms_per_step: wall time of a whole pass; kernel_ms_per_step: the kernels' own (HIP events)."""
+    from aresdb_amd import check
+    shard = workload.c3_shard(rows, batch_rows, seed=1, device=dev, quantised=False)
+    names = [n for n, _ in workload.C3_COLUMNS]
+    plan = queries.c3_plan(use_hash_reduction=False)
+    vps = [({k: rc.vp for k, rc in b.items()}, b["m"].length) for b in shard]
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    packed = None
+    def run():
+        nonlocal packed
+        q = NativeQuery(be, plan, names, streams=streams)
+        if packed is None:
+            packed = q.pack_batches(vps)
+        q.run_batches(packed)
+        return q
+    compiles = -1
+    for _ in range(4):  # priming passes: the shape's scan is compiled in the background — until a pass builds nothing new
+        run().release()
+        state = be.rtc_wait()
+        if state is None or state["compiles"] == compiles:
+            break
+        compiles = state["compiles"]
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    for _ in range(steps):
+        run().release()
+    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+    be.profiler_enable(True)
+    q = run(); torch.cuda.synchronize()
+    kernels = be.profiler_report(); be.profiler_enable(False)
+    groups = q.result_size
+    rep = check.compare_result(q.fetch(), check.exact_groups(shard), hash_identity=False, rel=1e-6, ordered=True)
+    q.release()
+    bytes_per_row = 5 * (4 + 1 / 8)
+    return [{"config": "c3-sort-float", "query": "SUM(m) float64 via Sort+Reduce", "float_aggregates_fused": os.environ.get("ARES_SR_FLOAT", "1") != "0",
+             "rows": rows, "batches": len(vps), "batch_rows": batch_rows, "groups": groups, "key_level_and_order_check_rel_1e-6": rep["status"],
+             "ms_per_step": dt * 1e3, "ms_per_1e9_rows": dt * 1e3 * 1e9 / rows, "rows_per_s": rows / dt, "algorithmic_bytes_per_row": bytes_per_row,
+             "kernel_ms_per_step": sum(ms for c, ms in kernels.values()),
+             "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}]
+
+
 def hll(be, dev, rows, groups, users, batches=2):
     """countdistincthll(user) group by g: `batches` batches of `rows` rows through the C++ driver."""
     from aresdb_amd.executor import Unary
@@ -444,6 +490,7 @@ def main():
     if "trips" in which: res += trips_leg(be, dev, int(float(os.environ.get("TRIPS_ROWS", "1e9"))))
     for leg in ("c3int64", "uuid"):
         if leg in which: res += wide_key_legs(be, dev, leg, int(float(os.environ.get("WIDE_ROWS", str(1 << 28)))))
+    if "c3sortfloat" in which: res += sort_float_leg(be, dev, int(float(os.environ.get("SORT_FLOAT_ROWS", "1e9"))))
     if "hll" in which:
         res += hll(be, dev, 1 << 25, 1000, 5_000_000) + hll(be, dev, 1 << 25, 4, 50_000_000) + hll(be, dev, 1 << 25, 100, 50_000_000, batches=4)
     if "geo" in which: res += geo(be, dev, 1 << 24, 100, 20) + geo(be, dev, 1 << 22, 250, 400)

@@ -133,6 +133,20 @@ int main(int argc, char **argv) {
     FusedPlanD m8 = p;
     m8.measure.f = col(K_U32); m8.measure.outKind = K_I32; m8.measureDtype = Int64; m8.measureWidth = 8;
     if (int rc = build(rtc_sort_scan_source(m8, 4, 9), "_sort_sum8", "sort scan (SUM into 8 bytes)")) return rc;
+    // float measures on the same path: SUM(m) of a Float32 column into float64 (the C3 plan's own measure: the headline query
+    // with enable_hash_reduction off), MIN_FLOAT into 4 bytes, SUM(m * 1.5); a float column times an INTEGER constant is declined
+    if (int rc = build(rtc_sort_scan_source(p, 4, 9), "_sort_fsum8", "sort scan (SUM_FLOAT into 8 bytes)")) return rc;
+    FusedPlanD f4 = p;
+    f4.measureDtype = Float32; f4.measureWidth = 4; f4.identity = 0x7f7fffffu;  // (FLT_MAX: MIN_FLOAT's null)
+    if (int rc = build(rtc_sort_scan_source(f4, 4, 9), "_sort_fmin", "sort scan (MIN_FLOAT)")) return rc;
+    FusedPlanD fx = p;
+    fx.measure.f.arity = 2; fx.measure.f.functor = Multiply; fx.measure.f.bkind = K_F32; fx.measure.f.bbits = 0x3fc00000u; fx.measure.f.bok = 1;
+    if (int rc = build(rtc_sort_scan_source(fx, 4, 9), "_sort_fexpr", "sort scan (float expression)")) return rc;
+    fx.measure.f.bkind = K_I32; fx.measure.f.bbits = 2;
+    if (!rtc_sort_scan_source(fx, 4, 9).empty()) { puts("a float column times an integer constant must be declined"); return 23; }
+    FusedPlanD i4 = f4;  // an integer column stored into a float measure: declined (the transform converts, a record would not)
+    i4.measure.f = col(K_U32);
+    if (!rtc_sort_scan_source(i4, 4, 9).empty()) { puts("an integer column into a 4-byte float measure must be declined"); return 24; }
     FusedPlanD t = p;  // trips: dims [Floor(request_at, 3600) Uint32, city_id Uint16 -> 2-byte slot], COUNT(*), three filters
     t.numCols = 3;
     t.cols[0].step = 4; t.cols[1].step = 2; t.cols[2].step = 1;
