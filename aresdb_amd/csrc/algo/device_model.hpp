@@ -233,16 +233,15 @@ __device__ __forceinline__ uint32_t week_start(uint32_t ts) {
   return ts - (ts - fourDays) % week;
 }
 
-// GetHLLValue (query/functor.hpp:431-466): rho<<16 | register, from the 64-bit hash
+// GetHLLValue (query/functor.hpp:431-466): rho<<16 | register, from the 64-bit hash.
+// The original counts rho while `hashed & (1 << (rho + HLL_BITS))` is zero and rho + HLL_BITS < 64.  Its 1 is a 32-bit int, so
+// only bits 14 ... 31 of the LOW word are ever probed; once the count reaches 32 the mask is empty in both of the reference's
+// builds (PTX shl clamps the count, the optimised x86-64 host code shifts in a 64-bit register and truncates), and rho runs on
+// to 64 - HLL_BITS.  It does not wrap into the register bits.
 __device__ __forceinline__ uint32_t hll_from_hash(uint64_t hashed) {
   const uint32_t group = static_cast<uint32_t>(hashed & ((1u << HLL_BITS) - 1));
-  uint32_t rho = 0;
-  for (;;) {
-    // 32-bit int shift of the original: count wraps mod 32, only the low word is probed
-    const uint32_t h = static_cast<uint32_t>(hashed) & (1u << ((rho + HLL_BITS) & 31));
-    if (rho + HLL_BITS < 64 && h == 0) rho++;
-    else break;
-  }
+  const uint32_t probed = static_cast<uint32_t>(hashed) >> HLL_BITS;
+  const uint32_t rho = probed ? static_cast<uint32_t>(__builtin_ctz(probed)) : 64u - HLL_BITS;
   return rho << 16 | group;
 }
 

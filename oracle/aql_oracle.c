@@ -474,14 +474,11 @@ static Val hll_value(Val t) { /* functor.hpp:431-466 */
     hashed = out[0];
   }
   uint32_t group = (uint32_t)(hashed & ((1 << HLL_BITS) - 1));
+  /* the original tests `hashed & (1 << (rho + HLL_BITS))` while rho + HLL_BITS < 64, with a 32-bit int 1: bits 14 ... 31 of the
+   * low word are probed; from a shift count of 32 on the mask is empty in both of the reference's builds (PTX clamps the count,
+   * its optimised x86-64 host code shifts in a 64-bit register and truncates), so rho runs on to 64 - HLL_BITS */
   uint32_t rho = 0;
-  for (;;) {
-    /* the original tests `hashed & (1 << (rho + HLL_BITS))` with a 32-bit int shift: the
-     * shift count wraps mod 32 and bit 31 sign-extends, so only the low word is ever probed */
-    uint32_t h = (uint32_t)(hashed & (uint64_t)(int64_t)(int32_t)(1u << ((rho + HLL_BITS) & 31)));
-    if (rho + HLL_BITS < 64 && h == 0) rho++;
-    else break;
-  }
+  while (rho + HLL_BITS < 64 && (rho + HLL_BITS >= 32 || (((uint32_t)hashed >> (rho + HLL_BITS)) & 1u) == 0)) rho++;
   return mk_u32(rho << 16 | group, true);
 }
 

@@ -15,25 +15,32 @@ The semantics restated here (as aresdb_amd/csrc/algo/device_model.hpp cites them
   * dimension / scratch / measure sinks               query/iterator.hpp:465-537, 616-727
   * identities of the aggregates                      query/utils.hpp:165-184
   * aggregation of measures                           query/functor.hpp:1380-1436, query/sort_reduce.cu:135-160
-Calendar functors, HyperLogLog, geo and the wide kinds are outside this model.
+  * calendar functors                                  query/functor.cu:70-212 (here: from the proleptic Gregorian calendar)
+  * GetHLLValue                                        query/functor.hpp:431-466, MurmurHash3_x64_128 as published
+Geo, the HyperLogLog aggregate and the arithmetic of the wide kinds are outside this model (unary_wide carries the wide
+inputs of the calendar functors and of GetHLLValue only).
 """
 import numpy as np
 
 # ---- enumerations of the C ABI (include/ares_algorithm.h), restated so that this module imports nothing ----
 (Bool, Int8, Uint8, Int16, Uint16, Int32, Uint32, Float32, Int64, Uint64, Float64, GeoPoint, UUID) = range(13)
-(Negate, Not, BitwiseNot, IsNull, IsNotNull, Noop) = range(6)
+(Negate, Not, BitwiseNot, IsNull, IsNotNull, Noop, GetWeekStart, GetMonthStart, GetQuarterStart, GetYearStart, GetDayOfMonth,
+ GetDayOfYear, GetMonthOfYear, GetQuarterOfYear, GetHLLValue) = range(15)
 (And, Or, Equal, NotEqual, LessThan, LessThanOrEqual, GreaterThan, GreaterThanOrEqual, Plus, Minus, Multiply, Divide,
  Mod, BitwiseAnd, BitwiseOr, BitwiseXor, Floor) = range(17)
 SUM_UNSIGNED, SUM_SIGNED, SUM_FLOAT, MIN_UNSIGNED, MIN_SIGNED, MIN_FLOAT, MAX_UNSIGNED, MAX_SIGNED, MAX_FLOAT = range(1, 10)
-AVG_FLOAT = 11
+AGGR_HLL, AVG_FLOAT = 10, 11
 
 UNARY = (Negate, Not, BitwiseNot, IsNull, IsNotNull, Noop)
+CALENDAR = (GetWeekStart, GetMonthStart, GetQuarterStart, GetYearStart, GetDayOfMonth, GetDayOfYear, GetMonthOfYear, GetQuarterOfYear)
+HLL_VALUE = (GetHLLValue,)
 BINARY = tuple(range(And, Floor + 1))
 COMPARISONS = tuple(range(Equal, GreaterThanOrEqual + 1))
-FUNCTOR_NAMES = {1: ["Negate", "Not", "BitwiseNot", "IsNull", "IsNotNull", "Noop"],
+FUNCTOR_NAMES = {1: ["Negate", "Not", "BitwiseNot", "IsNull", "IsNotNull", "Noop", "GetWeekStart", "GetMonthStart", "GetQuarterStart",
+                     "GetYearStart", "GetDayOfMonth", "GetDayOfYear", "GetMonthOfYear", "GetQuarterOfYear", "GetHLLValue"],
                  2: ["And", "Or", "Equal", "NotEqual", "LessThan", "LessThanOrEqual", "GreaterThan", "GreaterThanOrEqual", "Plus",
                      "Minus", "Multiply", "Divide", "Mod", "BitwiseAnd", "BitwiseOr", "BitwiseXor", "Floor"]}
-TYPE_NAMES = ["Bool", "Int8", "Uint8", "Int16", "Uint16", "Int32", "Uint32", "Float32", "Int64", "Uint64", "Float64"]
+TYPE_NAMES = ["Bool", "Int8", "Uint8", "Int16", "Uint16", "Int32", "Uint32", "Float32", "Int64", "Uint64", "Float64", "GeoPoint", "UUID"]
 
 K_BOOL, K_I32, K_U32, K_F32 = range(4)
 KIND_NAMES = ["bool", "int32", "uint32", "float32"]
@@ -146,7 +153,128 @@ def convert_defined(bits, from_kind, to_kind):
 
 
 def unary_result_kind(ft, kind):
+    if ft in CALENDAR or ft in HLL_VALUE:   # (the float specialisation hands its argument back)
+        return K_F32 if kind == K_F32 else K_U32
     return K_BOOL if ft in (Not, IsNull, IsNotNull) else kind
+
+
+# ---- calendar: proleptic Gregorian, UTC, no leap seconds; numpy's datetime64 is the calendar here ------------------------
+SECONDS_PER_DAY = 86400
+FOUR_DAYS = 4 * SECONDS_PER_DAY   # 1970-01-05, the first Monday of the epoch
+
+
+def _epoch_seconds(d):
+    return d.astype("datetime64[s]").astype(np.int64)
+
+
+def calendar(ft, ts):
+    """the calendar functor `ft` of epoch seconds `ts` (uint32 bits read as unsigned: 1970-01-01 ... 2106-02-07), mod 2^32"""
+    ts = np.asarray(ts, np.uint32).astype(np.int64)
+    if ft == GetWeekStart:   # 1970-01-01 was a Thursday; the days before the epoch's first Monday belong to "week 0"
+        day = ts // SECONDS_PER_DAY
+        monday = day - (day + 3) % 7
+        return u32(np.where(ts < FOUR_DAYS, 0, monday * SECONDS_PER_DAY))
+    t = ts.astype("datetime64[s]")
+    day, month, year = t.astype("datetime64[D]"), t.astype("datetime64[M]"), t.astype("datetime64[Y]")
+    months = month.astype(np.int64)          # months since 1970-01
+    month_of_year = months % 12
+    if ft == GetMonthStart:
+        return u32(_epoch_seconds(month))
+    if ft == GetQuarterStart:
+        return u32(_epoch_seconds((months - month_of_year % 3).astype("datetime64[M]")))
+    if ft == GetYearStart:
+        return u32(_epoch_seconds(year))
+    if ft == GetDayOfMonth:
+        return u32((day - month.astype("datetime64[D]")).astype(np.int64))
+    if ft == GetDayOfYear:
+        return u32((day - year.astype("datetime64[D]")).astype(np.int64))
+    if ft == GetMonthOfYear:
+        return u32(month_of_year)
+    if ft == GetQuarterOfYear:
+        return u32(month_of_year // 3)
+    raise ValueError(ft)
+
+
+# ---- GetHLLValue ---------------------------------------------------------------------------------------------------------
+M64 = 0xFFFFFFFFFFFFFFFF
+HLL_BITS = 14
+
+
+def _c64(x, like):
+    return np.uint64(x) if isinstance(like, np.ndarray) else x
+
+
+def _rotl64(x, r):
+    return ((x << _c64(r, x)) | (x >> _c64(64 - r, x))) & _c64(M64, x)
+
+
+def _fmix64(k):
+    k = k ^ (k >> _c64(33, k))
+    k = (k * _c64(0xff51afd7ed558ccd, k)) & _c64(M64, k)
+    k = k ^ (k >> _c64(33, k))
+    k = (k * _c64(0xc4ceb9fe1a85ec53, k)) & _c64(M64, k)
+    return k ^ (k >> _c64(33, k))
+
+
+def murmur3_x64_128_low(key, nbytes, seed=0):
+    """low 64 bits (h1) of MurmurHash3_x64_128 of a key of `nbytes` < 16 bytes given as its little-endian integer (so the key
+    is all "tail": no 16-byte block, and with at most 8 bytes only k1 is mixed).  `key` is a Python int or a numpy uint64 array:
+    the arithmetic is mod 2^64 either way."""
+    assert 0 < nbytes <= 8
+    c1, c2 = 0x87c37b91114253d5, 0x4cf5ad432745937f
+    with np.errstate(over="ignore"):
+        k1 = (key * _c64(c1, key)) & _c64(M64, key)
+        k1 = (_rotl64(k1, 31) * _c64(c2, key)) & _c64(M64, key)
+        h1 = _c64(seed, key) ^ k1
+        h2 = _c64(seed, key) ^ (key ^ key)
+        h1, h2 = h1 ^ _c64(nbytes, key), h2 ^ _c64(nbytes, key)
+        h1 = (h1 + h2) & _c64(M64, key)
+        h2 = (h2 + h1) & _c64(M64, key)
+        h1, h2 = _fmix64(h1), _fmix64(h2)
+        return (h1 + h2) & _c64(M64, key)
+
+
+def hll_from_hash(h):
+    """rho << 16 | register of 64-bit hashes (numpy uint64).  register = the low 14 bits.  rho is the number of probes that find
+    a clear bit; probe number rho looks at bit rho + 14 of the hash, for rho + 14 < 64.  The original builds the probe mask by
+    shifting a 32-bit 1, so it can only ever look at the LOW 32 bits: bits 14 ... 31 are real probes (rho = 0 ... 17); from bit 32
+    on the shift count exceeds the 32-bit type and the mask is empty in both of the reference's builds (x86-64 host code
+    compiled with optimisation, and PTX, whose shl clamps the count), so every later probe finds "clear" and rho runs on to 50.
+    rho is the number of trailing zeros of bits 14 ... 31 of the low word, or 50 when all of them are clear; the high word and
+    the register bits never count.  (A mask whose shift count wraps mod 32 would probe the register bits again from rho = 18:
+    that reading is none of the reference's builds, and test_calendar_hll_semantics.py holds the inputs that tell it apart.)"""
+    h = np.asarray(h, np.uint64)
+    low = (h & np.uint64(M32)).astype(np.int64)
+    up = low >> HLL_BITS
+    lowest = up & -up                                     # the lowest set bit, a power of two below 2^18: exact in float64
+    rho = np.where(up == 0, 64 - HLL_BITS, np.log2(np.maximum(lowest, 1).astype(np.float64)).astype(np.int64))
+    return u32((rho << 16) | (low & ((1 << HLL_BITS) - 1)))
+
+
+def hll_value(kind, bits):
+    """GetHLLValue of a 32-bit kind: a Bool hashes its one byte, every other kind the four bytes of its widened value"""
+    key = np.asarray(bits, np.uint32).astype(np.uint64)
+    return hll_from_hash(murmur3_x64_128_low(key, 1 if kind == K_BOOL else 4))
+
+
+def unary_wide(ft, dtype, lo, hi, ok):
+    """(bits, validity) of a calendar functor or GetHLLValue over a wide column; the result is of kind K_U32.
+    lo / hi: the value's low and high 8 bytes as uint64 (hi only for UUID; GeoPoint: lo = latitude | longitude << 32).
+    Int64: the calendar functors see the low 32 bits, GetHLLValue hashes the 8 bytes.  UUID: GetHLLValue takes lo ^ hi as the
+    hash, unhashed; every calendar functor is null.  GeoPoint: always null."""
+    lo, ok = np.asarray(lo, np.uint64), np.asarray(ok, bool)
+    zero = np.zeros(lo.shape, np.uint32)
+    if ft not in CALENDAR and ft not in HLL_VALUE:
+        raise ValueError(ft)
+    if dtype == Int64:
+        r = calendar(ft, (lo & np.uint64(M32)).astype(np.uint32)) if ft in CALENDAR else hll_from_hash(murmur3_x64_128_low(lo, 8))
+    elif dtype == UUID and ft == GetHLLValue:
+        r = hll_from_hash(lo ^ np.asarray(hi, np.uint64))
+    elif dtype in (UUID, GeoPoint):
+        return zero, np.zeros(lo.shape, bool)
+    else:
+        raise ValueError(dtype)
+    return np.where(ok, r, zero).astype(np.uint32), ok
 
 
 def unary(ft, kind, v, ok):
@@ -173,6 +301,12 @@ def unary(ft, kind, v, ok):
         if kind == K_F32:      # the float specialisation hands its argument back
             return v, ok
         r = np.ones(v.shape, np.uint32) if kind == K_BOOL else ~v
+        return np.where(ok, r, zero).astype(np.uint32), ok
+    if ft in CALENDAR or ft in HLL_VALUE:
+        if kind == K_F32:      # the float specialisation hands its argument back, kind and validity included
+            return v, ok
+        # (a negative Int32, or a sign-extended Int8 / Int16, converts to the uint32 kind bit for bit: a date after 2038)
+        r = calendar(ft, convert(v, kind, K_U32)) if ft in CALENDAR else hll_value(kind, v)
         return np.where(ok, r, zero).astype(np.uint32), ok
     raise ValueError(ft)
 

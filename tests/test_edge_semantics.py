@@ -62,8 +62,9 @@ class Vec:
             return M.K_F32
         return M.KIND_OF[self.dtype]
 
-    def rows(self, rows, n):
-        """(bits, validity) at output positions 0..n-1 whose table rows are `rows`"""
+    def rows(self, rows, n, located=None):
+        """(bits, validity) at output positions 0..n-1 whose table rows are `rows`; `located`: where the call's baseCounts /
+        startCount put those rows in a run-length column's uncompressed space (the rows themselves by default)"""
         if self.kind == "cint":
             return np.full(n, M.u32(self.value), np.uint32), np.full(n, self.const_valid)
         if self.kind == "cfloat":
@@ -73,7 +74,7 @@ class Vec:
         if self.mode == 0:   # the column is its default value
             return np.full(n, M.widen(np.array([self.value if self.value is not None else 0]), self.dtype)[0], np.uint32), \
                 np.full(n, self.value is not None)
-        phys = np.searchsorted(self.counts, rows, side="right") - 1 if self.mode == 3 else rows
+        phys = np.searchsorted(self.counts, rows if located is None else located, side="right") - 1 if self.mode == 3 else rows
         bits = M.widen(self.values, self.dtype)[phys]
         return bits, (np.ones(n, bool) if self.valid is None else np.asarray(self.valid, bool)[phys])
 
@@ -121,8 +122,9 @@ class EdgeCase:
     """One ABI call over prepared operands, with the `run(be) -> dict` contract of tests/cases.py, and `expect()`: the same
     dict from the model."""
 
-    def __init__(self, a, b, functor, sink, index, base_counts=None, init_index=False):
+    def __init__(self, a, b, functor, sink, index, base_counts=None, init_index=False, start_count=0, locate=False):
         self.a, self.b, self.functor, self.sink = a, b, functor, sink
+        self.start_count, self.locate = start_count, locate or start_count != 0   # locate: run-length operands follow base_counts
         self.index, self.n, self.base_counts, self.init_index = np.asarray(index, np.uint32), len(index), base_counts, init_index
 
     def __repr__(self):
@@ -132,7 +134,9 @@ class EdgeCase:
     def evaluate(self):
         """(result bits, validity, result kind, a bits, b bits, common kind) per output position"""
         rows = self.index.astype(np.int64)
-        a, aok = self.a.rows(rows, self.n)
+        located = None if not self.locate else self.base_counts.astype(np.int64)[rows] if self.base_counts is not None \
+            else rows + self.start_count
+        a, aok = self.a.rows(rows, self.n, located)
         if self.b is None:
             k = self.a.model_kind()
             r, ok = M.unary(self.functor, k, a, aok)
@@ -177,7 +181,7 @@ class EdgeCase:
             if self.init_index:   # an index vector the library has numbered itself: filters are counted in row space
                 be.call("InitIndexVector", idx.ptr, 0, n, None, 0)
             res["count"] = be.call("UnaryFilter" if self.b is None else "BinaryFilter", *ins, idx.ptr, pred.ptr, n, None, 0,
-                                   bc.ptr if bc else None, 0, self.functor, None, 0)
+                                   bc.ptr if bc else None, self.start_count, self.functor, None, 0)
             res["pred"] = pred.read(np.uint8, n + 8)
             res["index"] = idx.read(np.uint32, res["count"])
         else:
@@ -199,7 +203,7 @@ class EdgeCase:
                     ov = H.measure_output(vb.ptr + w * off, s.dtype, s.agg)
                     read = lambda: {"values": vb.read(np.uint8, w * (n + off) + 8)}  # noqa: E731
             res["ret"] = be.call("UnaryTransform" if self.b is None else "BinaryTransform", *ins, ov, idx.ptr, n,
-                                 bc.ptr if bc else None, 0, self.functor, None, 0)
+                                 bc.ptr if bc else None, self.start_count, self.functor, None, 0)
             res.update(read())
         for k in keep:
             k.free()
