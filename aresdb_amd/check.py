@@ -359,3 +359,74 @@ def hash_groups_of_rows(values, valids, measures):
     for i, r in enumerate(rep):
         out[tuple((int(values[d][r]), int(valids[d][r])) for d in range(4))] = sums[i]
     return out
+
+
+# ---- AVG(m): mean per key ------------------------------------------------------------------------------------------------
+def exact_means(batches, dims=ALL_DIMS, d1_below=90, ts_range=None):
+    """Exact AVG(m) of the C3 query per key: numpy (code, mean, valid_rows, abs_sum, first_row).  valid_rows counts the
+    group's rows whose measure is not null — the count AVG_FLOAT carries beside its average; a group of null-measure rows
+    only exists with valid_rows 0 and mean 0.  abs_sum = sum|m| over the valid rows: what the average's tolerance scales by."""
+    dev = batches[0]["m"].blob.device
+    space = key_space(dims)
+    salt = 1 if space >= (1 << 20) else max(1, min(8192, (1 << 24) // space))
+    acc = torch.zeros(space * salt, dtype=torch.float64, device=dev)
+    mag = torch.zeros(space * salt, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(space * salt, dtype=torch.int64, device=dev)
+    rows_of = torch.zeros(space * salt, dtype=torch.int64, device=dev)
+    first = torch.full((space * salt,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev)
+    offset = 0
+    for b in batches:
+        c, keep, mm = _codes_of_batch(b, None, dims, d1_below, ts_range)  # (a null measure: 0)
+        ok = b["m"].valid()
+        rows = torch.arange(offset, offset + c.numel(), dtype=torch.int64, device=dev)[keep]
+        idx = c[keep]
+        if salt > 1:
+            idx = idx * salt + rows % salt
+        acc.index_add_(0, idx, mm[keep])
+        mag.index_add_(0, idx, mm[keep].abs())
+        cnt.index_add_(0, idx, torch.ones_like(idx) if ok is None else ok[keep].to(torch.int64))
+        rows_of.index_add_(0, idx, torch.ones_like(idx))
+        first.scatter_reduce_(0, idx, rows, reduce="amin", include_self=True)
+        offset += c.numel()
+        del c, keep, mm, idx, rows
+    if salt > 1:
+        acc, mag, cnt, rows_of = (x.view(space, salt).sum(dim=1) for x in (acc, mag, cnt, rows_of))
+        first = first.view(space, salt).amin(dim=1)
+    live = torch.nonzero(rows_of > 0).reshape(-1)
+    mean = acc[live] / cnt[live].clamp(min=1).to(torch.float64)
+    return live.cpu().numpy(), mean.cpu().numpy(), cnt[live].cpu().numpy(), mag[live].cpu().numpy(), first[live].cpu().numpy()
+
+
+def compare_means(got_code, pairs, expected, rel=1e-4):
+    """got_code: dense key codes of the fetched rows; pairs: the fetched AVG_FLOAT measures, 8 bytes per group {f32 average,
+    u32 count}; expected = (code, mean, valid_rows, abs_sum, ...).  Same keys, every count exact, every average within
+    rel * sum|m| / max(count, 1) of the exact mean (the float32-accumulator bound of INTEGRATION.md).  None, or a description."""
+    code, mean, valid_rows, abs_sum = expected[:4]
+    p = np.frombuffer(pairs, np.uint32).reshape(-1, 2)
+    if len(got_code) != len(code):
+        return f"group count {len(got_code)} != expected {len(code)}"
+    go, wo = np.argsort(got_code, kind="stable"), np.argsort(code, kind="stable")
+    if (got_code[go] != code[wo]).any():
+        return f"{int((got_code[go] != code[wo]).sum())} dimension rows differ"
+    avg, count = p[:, 0].copy().view(np.float32).astype(np.float64)[go], p[:, 1][go].astype(np.int64)
+    bad = np.nonzero(count != valid_rows[wo])[0]
+    if len(bad):
+        return f"{len(bad)} counts differ (first: key {code[wo][bad[0]]} got {count[bad[0]]} expected {valid_rows[wo][bad[0]]})"
+    bad = np.nonzero(~(np.abs(avg - mean[wo]) <= rel * abs_sum[wo] / np.maximum(valid_rows[wo], 1)))[0]
+    if len(bad):
+        return f"{len(bad)} averages differ (first: key {code[wo][bad[0]]} got {avg[bad[0]]!r} expected {mean[wo][bad[0]]!r})"
+    return None
+
+
+def compare_mean_result(fetched, expected, dims=ALL_DIMS, rel=1e-4):
+    """fetched = NativeQuery.fetch() of an AVG(m) query through Sort + Reduce; expected = exact_means(...): keys, counts,
+    averages (compare_means) and the rows in strictly ascending order of their 64-bit row hash.  Returns a report dict."""
+    dims_, valids, meas = fetched
+    got_code = encode_rows([np.frombuffer(d, np.uint32) for d in dims_], [np.frombuffer(v, np.uint8) for v in valids], dims)
+    why = compare_means(got_code, meas, expected, rel)
+    if why is None and len(got_code) > 1:
+        h = row_hashes_of_fetched(dims_, valids)
+        if not (h[1:] > h[:-1]).all():
+            why = f"rows are not in ascending order of their 64-bit hash (first descent at row {int(np.nonzero(h[1:] <= h[:-1])[0][0]) + 1})"
+    return {"status": "ok" if why is None else "MISMATCH: " + why, "groups": int(len(got_code)), "expected_groups": int(len(expected[0])),
+            "groups_without_a_valid_measure": int((expected[2] == 0).sum())}

@@ -502,6 +502,19 @@ __device__ __forceinline__ double to_double32(DVal r, int rk) {
          : rk == K_I32 ? static_cast<double>(static_cast<int32_t>(r.bits)) : static_cast<double>(r.bits);
 }
 
+// the average a valid row starts AVG_FLOAT's {f32 average, u32 count} pair with: the value as the measure's type, then as a float
+__device__ __forceinline__ float avg_measure_float(int dtype, DVal r, int rk) {
+  switch (dtype) {
+    case Float64: return static_cast<float>(to_double32(r, rk));
+    case Int64: return rk == K_F32 ? static_cast<float>(static_cast<int64_t>(bits_f(r.bits)))
+                       : rk == K_I32 ? static_cast<float>(static_cast<int64_t>(static_cast<int32_t>(r.bits)))
+                                     : static_cast<float>(static_cast<int64_t>(r.bits));
+    case Int32: return static_cast<float>(static_cast<int32_t>(cvt32(r, rk, K_I32).bits));
+    case Uint32: return static_cast<float>(cvt32(r, rk, K_U32).bits);
+    default: return bits_f(cvt32(r, rk, K_F32).bits);
+  }
+}
+
 // MeasureProxy (query/iterator.hpp:616-647): null -> identity; SUM/AVG scale by the run length
 __device__ __forceinline__ void store_measure32(const SinkD &s, uint32_t i, uint32_t row, DVal r, int rk) {
   uint8_t *dst = s.values + static_cast<size_t>(s.width) * i;
@@ -515,18 +528,7 @@ __device__ __forceinline__ void store_measure32(const SinkD &s, uint32_t i, uint
   uint32_t count = 1;
   if (scaled && s.baseCounts) count = s.baseCounts[row + 1] - s.baseCounts[row];
   if (isAvg) {
-    float f;
-    switch (s.dtype) {
-      case Float64: f = static_cast<float>(to_double32(r, rk)); break;
-      case Int64: f = rk == K_F32 ? static_cast<float>(static_cast<int64_t>(bits_f(r.bits)))
-                      : rk == K_I32 ? static_cast<float>(static_cast<int64_t>(static_cast<int32_t>(r.bits)))
-                                    : static_cast<float>(static_cast<int64_t>(r.bits));
-        break;
-      case Int32: f = static_cast<float>(static_cast<int32_t>(cvt32(r, rk, K_I32).bits)); break;
-      case Uint32: f = static_cast<float>(cvt32(r, rk, K_U32).bits); break;
-      default: f = bits_f(cvt32(r, rk, K_F32).bits); break;
-    }
-    reinterpret_cast<uint32_t *>(dst)[0] = f_bits(f);
+    reinterpret_cast<uint32_t *>(dst)[0] = f_bits(avg_measure_float(s.dtype, r, rk));
     reinterpret_cast<uint32_t *>(dst)[1] = count;
     return;
   }

@@ -64,6 +64,10 @@ struct FusedPlanD {
   // Plans with a narrow slot or a narrow column ("narrow plans") run on the kernels generated for their shape only
   // (hr_rtc.hip); the precompiled generic kernels read 4-byte columns and write 4-byte slots.
   uint8_t dimWidth[kFusedDims];
+  // AVG_FLOAT (Sort + Reduce only): the measure's record carries the FLOAT the measure transform would have stored as the
+  // pair's average — the value as measureDtype, then as a float (avg_measure_float) — and the top bit of its row word says
+  // "null measure": the pair {0, 0} instead of {average, 1}
+  int measureAvg;
 };
 inline int fused_dim_width(const FusedPlanD &p, int d) { return p.dimWidth[d] ? p.dimWidth[d] : 4; }
 inline int fused_col_step(const FusedPlanD &p, int c) { return p.cols[c].step ? static_cast<int>(p.cols[c].step) : 4; }
@@ -125,6 +129,7 @@ inline void fused_plan_measure(FusedPlanD &plan, int nd, const FastOperands &f, 
   plan.measureDtype = sink.dtype;
   plan.measureWidth = valueBytes;
   plan.identity = sink.identity;
+  plan.measureAvg = sink.agg == AGGR_AVG_FLOAT ? 1 : 0;
   plan.numCols = nd + 1;
 }
 // ... or a constant (Sort + Reduce: COUNT(*)): no column

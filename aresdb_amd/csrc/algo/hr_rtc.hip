@@ -306,8 +306,9 @@ bool gen_agg(std::ostringstream &o, const AggSpec &a) {
 // by 8 adjacent lanes with one store; the < 8 records a partition has left over stay in LDS and go first in
 // the next tile's lines.  Streams are private to the workgroup: no global atomics.
 // part: the partition of row j's hash (default: its top PB bits)
+// row: the record's first word (AVG_FLOAT's scan sets its top bit for a null measure: generate)
 static void kernel_body_lines16(std::ostringstream &o, const char *fourth, const char *entry = "hr_scan_rtc",
-                                const char *part = "(PB ? hh[j] >> (32 - (PB ? PB : 1)) : 0u)") {
+                                const char *part = "(PB ? hh[j] >> (32 - (PB ? PB : 1)) : 0u)", const char *row = "a.rowBase + i0 + j") {
   phase_macros(o);
   o << "#define T 4096u\n"
        "__device__ __forceinline__ u32 lane_up(u32 v, u32 lane, u32 off) { return (u32)__builtin_amdgcn_ds_bpermute((int)((lane - off) << 2), (int)v); }\n"
@@ -365,7 +366,7 @@ static void kernel_body_lines16(std::ostringstream &o, const char *fourth, const
        "    PH(1)\n"
        "#pragma unroll\n"
        "    for (int j = 0; j < 4; j++)\n"
-       "      if (alive[j]) sRec[sStart[" << part << "] + rank[j]] = make_uint4(a.rowBase + i0 + j, hh[j], cv[j], " << fourth << ");\n"
+       "      if (alive[j]) sRec[sStart[" << part << "] + rank[j]] = make_uint4(" << row << ", hh[j], cv[j], " << fourth << ");\n"
        "    __syncthreads();\n"
        "    PH(2)\n"
        // whole lines: 8 adjacent lanes write the 8 records of one aligned 128-byte line with one store;
@@ -885,6 +886,10 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
   const bool sort64 = kind == SCAN_SORT64;
   const bool constMeasure = sort64 && plan.measure.col < 0;  // the records carry Args::k's measure slot as it is
   if (plan.measure.col < 0 && !sort64) return "";
+  // AVG_FLOAT: the record carries the pair's average (a float, whatever the column's kind) and, in the top bit of its row word,
+  // "null measure" — a row index fits 31 bits, a stream's padding records stay row = ~0
+  const bool avg = plan.measureAvg != 0;
+  if (avg && (!sort64 || constMeasure || plan.measureWidth != 8 || plan.identity != 0)) return "";
   const int firstFilterCol = constMeasure ? nd : nd + 1;  // column slots: dimension d -> d, measure -> nd (if any), then the filters' own
   o << kPrelude << (sort64 ? kPrelude64 : "") << args_text()
     << "#define NC " << nc << "\n#define ND " << nd << "\n#define PB " << partBits << "\n#define NP " << (1 << partBits) << "\n"
@@ -967,7 +972,16 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
       o << "#pragma unroll\n  for (int j = 0; j < 4; j++) {\n"
            "    const u32 v = r.v[" << nd << "][j]; const u32 okb = (okc[" << nd << "] >> j) & 1u; u32 x;\n";
       if (!gen_value(e.f, o, "v", "okb", "x", const_name(const_slot_measure()), sort64)) return "";
-      if (plan.measureWidth == 8) {
+      if (avg) {  // avg_measure_float (device_model.hpp) of the expression's value: as measureDtype, then as a float
+        const int rk = e.f.rk;
+        if (!(rk == K_F32 || rk == K_I32 || rk == K_U32) || !(plan.measureDtype == Float64 || plan.measureDtype == Int64)) return "";
+        const bool f64 = plan.measureDtype == Float64;
+        const char *cvt = rk == K_F32 ? (f64 ? "x" : "__float_as_uint((float)(i64)__uint_as_float(x))")
+                          : rk == K_I32 ? (f64 ? "__float_as_uint((float)(double)(i32)x)" : "__float_as_uint((float)(i64)(i32)x)")
+                                        : (f64 ? "__float_as_uint((float)(double)x)" : "__float_as_uint((float)(i64)x)");
+        o << "    cv[j] = okb ? " << cvt << " : 0u;\n"
+             "    alive[j] |= (alive[j] & (okb ^ 1u)) << 31;\n";
+      } else if (plan.measureWidth == 8) {
         if (plan.identity != 0) return "";
         o << "    cv[j] = okb ? x : 0u;\n";
       } else {
@@ -1028,7 +1042,8 @@ std::string generate(const FusedPlanD &plan, int nd, int partBits, uint32_t null
   } else if (kind == SCAN_COMPACT) {
     kernel_body_compact(o);
   } else {
-    kernel_body_lines16(o, sort64 ? "cw[j]" : "0u", sort64 ? "sr_scan_rtc" : "hr_scan_rtc");
+    if (avg) kernel_body_lines16(o, "cw[j]", "sr_scan_rtc", "(PB ? hh[j] >> (32 - (PB ? PB : 1)) : 0u)", "(a.rowBase + i0 + j) | (alive[j] & 0x80000000u)");
+    else kernel_body_lines16(o, sort64 ? "cw[j]" : "0u", sort64 ? "sr_scan_rtc" : "hr_scan_rtc");
   }
   return o.str();
 }
@@ -2270,7 +2285,7 @@ std::string shape_key(char tag, int device, const FusedPlanD &plan, int nd, int 
   for (int i = 0; i < plan.numFilters && i < kFusedFilters; i++) put_expr(k, plan.filters[i]);
   for (int d = 0; d < nd && d < kFusedDims; d++) put_expr(k, plan.dims[d]);
   put_expr(k, plan.measure);
-  put(k, plan.measureDtype); put(k, plan.measureWidth); put(k, plan.identity);
+  put(k, plan.measureDtype); put(k, plan.measureWidth); put(k, plan.identity); put(k, plan.measureAvg);
   if (a) { put(k, a->vtype); put(k, a->op); put(k, a->width); put(k, a->identity); }
   if (w) { put(k, w->mode); put(k, w->rk); put(k, w->dtype); }
   return k;

@@ -27,7 +27,9 @@
 //   4. sr_emit_kernel      prefix over the partitions' group counts, dimension rows of the representatives gathered (previous
 //                          result) or re-evaluated from the source columns (batch rows), values stored: ascending hash order.
 // Float aggregates ride the same tables: SUM_FLOAT into 8 or 4 bytes, MIN_FLOAT, MAX_FLOAT (one LDS instruction per record,
-// like the integer ones) on both layouts, AVG_FLOAT (a compare-and-swap loop) on the wide one.  Their additions land in
+// like the integer ones) and AVG_FLOAT (a compare-and-swap loop on the packed {f32 average, u32 count}) on both layouts.  A
+// scan-fed AVG record carries the float the measure transform would have stored and, in the top bit of its row word, "null
+// measure": a batch row's pair is {that float, 1} or {0, 0}.  Their additions land in
 // whatever order the records arrive in: group count, order, representatives, dimension bytes, AVG's counts, MIN / MAX stay
 // bit-exact, a sum's last bits may differ from run to run — ARES_SR_FLOAT=0 gives the sorted order back (the real sort).
 // The real sort also takes anything this path declines: more groups than the partitions' tables hold, a skewed partition
@@ -224,8 +226,18 @@ __device__ __forceinline__ bool sr_unordered(uint64_t bits, const AggSpec &a) {
   return false;
 }
 
-template <int VW, bool WIDE, bool FLT>
+// AVG (scan-fed AVG_FLOAT: VW 8, FLT, not WIDE): a batch record's row word holds the row in its low 31 bits and "null measure"
+// in the top one (padding records stay ~0); its value is the pair {carried float, 1}, or {0, 0} for a null measure
+constexpr uint32_t kNullMeasure = 0x80000000u;
+template <bool AVG>
+__device__ __forceinline__ uint32_t sr_record_row(uint32_t word) { return AVG ? word & ~kNullMeasure : word; }
+__device__ __forceinline__ uint64_t sr_average_pair(uint32_t rowWord, uint32_t carried) {
+  return (rowWord & kNullMeasure) ? 0ull : (1ull << 32) | carried;
+}
+
+template <int VW, bool WIDE, bool FLT, bool AVG = false>
 __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrArgs m) {
+  static_assert(!AVG || (VW == 8 && FLT && !WIDE), "the scan-fed average: 8-byte float slots");
   using T = Table<VW, WIDE>;
   using V = typename Slots<VW>::V;
   __shared__ __attribute__((aligned(16))) uint64_t sKeys[T::kSlots];
@@ -324,11 +336,11 @@ __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrA
     }
     return -1;
   };
-  // (AVG_FLOAT reaches the wide layout only: its measure is never carried by a scan-fed record)
-  const bool average = FLT && WIDE && VW == 8 && a.vtype == V_AVG;
+  // (AVG_FLOAT: the wide layout gathers the pairs by row, the scan-fed instantiation builds them from its records)
+  const bool average = AVG || (FLT && WIDE && VW == 8 && a.vtype == V_AVG);
   auto settle = [&](int slot, uint32_t row, uint64_t value) {
     __hip_atomic_fetch_min(sRows + slot, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if constexpr (FLT && WIDE && VW == 8) {
+    if constexpr (AVG || (FLT && WIDE && VW == 8)) {
       if (average) {
         sr_average(reinterpret_cast<uint64_t *>(sVals + slot), value);
         return;
@@ -428,7 +440,8 @@ __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrA
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (static_cast<uint32_t>(lane) < count) {
         const uint4 q = queue[first + lane];
-        insert(q.x, q.y, q.w, m.constMeasure ? m.constBits : m.gatherValues ? load_value_bits(m.inValues, a, q.x) : hr::widen_value(m.widen, q.z));
+        if constexpr (AVG) insert(sr_record_row<true>(q.x), q.y, q.w, sr_average_pair(q.x, q.z));
+        else insert(q.x, q.y, q.w, m.constMeasure ? m.constBits : m.gatherValues ? load_value_bits(m.inValues, a, q.x) : hr::widen_value(m.widen, q.z));
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
@@ -453,10 +466,12 @@ __global__ __launch_bounds__((Table<VW, WIDE>::kLanes)) void sr_merge_kernel(SrA
         const bool m0 = u[k].x == lo && u[k].y == hi, m1 = u[k].z == lo && u[k].w == hi, m2 = v[k].x == lo && v[k].y == hi, m3 = v[k].z == lo && v[k].w == hi;
         const bool hit = valid && (m0 || m1 || m2 || m3) && (hi & lo) != 0xFFFFFFFFu;
         const uint32_t slot = hit ? 4u * bkt[k] + (m0 ? 0u : m1 ? 1u : m2 ? 2u : 3u) : static_cast<uint32_t>(T::kSlots);
-        const uint64_t value = m.constMeasure ? m.constBits : (WIDE && m.gatherValues) ? (valid ? load_value_bits(m.inValues, a, r[k].x) : 0ull) : hr::widen_value(m.widen, r[k].z);
+        const uint64_t value = AVG ? sr_average_pair(r[k].x, r[k].z)
+                               : m.constMeasure ? m.constBits : (WIDE && m.gatherValues) ? (valid ? load_value_bits(m.inValues, a, r[k].x) : 0ull) : hr::widen_value(m.widen, r[k].z);
+        const uint32_t row = sr_record_row<AVG>(r[k].x);
         // (the group's lowest row is settled after its first few records: a plain read tells the rest they need no atomic)
-        if (hit && r[k].x < sRows[slot]) __hip_atomic_fetch_min(sRows + slot, r[k].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if constexpr (FLT && WIDE && VW == 8) {
+        if (hit && row < sRows[slot]) __hip_atomic_fetch_min(sRows + slot, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if constexpr (AVG || (FLT && WIDE && VW == 8)) {
           if (average) {
             if (hit) sr_average(reinterpret_cast<uint64_t *>(sVals + slot), value);
           } else {
@@ -1104,14 +1119,16 @@ bool fused_sort_reduce_supported(const AggSpec &a) {
   if (a.vtype == V_U64 || a.vtype == V_I64) return a.op == OP_SUM;
   if (!float_aggregates_enabled()) return false;
   if (a.vtype == V_F32) return a.op == OP_SUM || a.op == OP_MIN || a.op == OP_MAX;
-  return (a.vtype == V_F64 && a.op == OP_SUM) || (a.vtype == V_AVG && a.op == OP_AVG);  // (AVG_FLOAT: the wide layout only)
+  return (a.vtype == V_F64 && a.op == OP_SUM) || (a.vtype == V_AVG && a.op == OP_AVG);
 }
 
 int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool constMeasure, uint64_t constBits, int batchRows,
                           const DimensionVector &in, const uint8_t *inValues, int prevSize, const DimensionVector &out,
                           uint8_t *outValues, const AggSpec &a, hipStream_t stream) {
   if (!fused_sort_reduce_enabled() || !fused_sort_reduce_supported(a) || batchRows <= 0 || prevSize < 0) return kFusedUnavailable;
-  if (a.vtype == V_AVG) return kFusedUnavailable;  // (a record carries 4 bytes: no room for {average, count})
+  // AVG_FLOAT: the batch's own pairs are {float, 1} or {0, 0} — 4 carried bytes and one bit (a constant measure, whose rows are
+  // a fill pattern, is never defined lazily for AVG)
+  if ((a.vtype == V_AVG) != (plan.measureAvg != 0) || (a.vtype == V_AVG && constMeasure)) return kFusedUnavailable;
   // ARES_SR_SCAN_FED=0 (tests): this path declines everything — its callers go on to the wide layout over materialised rows
   static EnvSwitch<bool> scanFed("ARES_SR_SCAN_FED", [](const char *e) { return !(e && e[0] == '0'); });
   if (!scanFed.get()) return kFusedUnavailable;
@@ -1202,7 +1219,8 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
   m.phases = merge_phase_stamps(numParts, stream);
   const bool flt = float_agg(a);
   if (vw == 8) {
-    if (flt) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false, true>), numParts, kThreads, stream, m);
+    if (a.vtype == V_AVG) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false, true, true>), numParts, kThreads, stream, m);
+    else if (flt) ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false, true>), numParts, kThreads, stream, m);
     else ARES_LAUNCH("sr_merge_kernel", (sr_merge_kernel<8, false, false>), numParts, kThreads, stream, m);
     ARES_LAUNCH("sr_emit_kernel", (sr_emit_kernel<8, false>), numParts, kThreads, stream, m, plan, L);
   } else {

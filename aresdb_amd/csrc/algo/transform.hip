@@ -1234,10 +1234,17 @@ static void forget_run_expansions(int device, const ByteRange &r) {
 
 static bool fast_sink(const SinkD &s) {
   const bool four = s.dtype == Int32 || s.dtype == Uint32 || s.dtype == Float32;
-  if (s.type == SINK_MEASURE) return s.agg != AGGR_AVG_FLOAT && s.baseCounts == nullptr;
+  // (AVG_FLOAT: its 8-byte {f32 average, u32 count} pairs; the expressions it takes: avg_hot_shape below)
+  if (s.type == SINK_MEASURE) return s.baseCounts == nullptr && (s.agg != AGGR_AVG_FLOAT || s.width == 8);
   // 1- / 2-byte dimension slots (city_id Uint16, status SmallEnum: query/common/dim_util.go:9-12) take integer results
   const bool narrow = s.type == SINK_DIM && (s.dtype == Int8 || s.dtype == Uint8 || s.dtype == Int16 || s.dtype == Uint16);
   return ((s.type == SINK_DIM || s.type == SINK_SCRATCH) && four) || narrow;
+}
+
+// An AVG_FLOAT measure is held back only where the Sort + Reduce scan can carry it (hr_rtc.hip, SCAN_SORT64): a bare column, or a
+// column combined with a constant by Plus / Minus / Multiply; anything else keeps the generic kernel it has always had.
+static bool avg_hot_shape(const FastOperands &f) {
+  return f.arity == 1 || (f.arity == 2 && !f.divLike && (f.functor == Plus || f.functor == Minus || f.functor == Multiply));
 }
 
 // Binds an array column and its functor (query/binder.hpp:385-426, :458-560): the second operand
@@ -1395,6 +1402,7 @@ static int run_transform(const InputVector *ins, int arity, const OutputVector &
   FastOperands f;
   bool fast = fast_sink(s) && fast_operands(p, f, false);
   if (fast && s.type == SINK_DIM && s.width < 4 && !(f.rk == K_I32 || f.rk == K_U32)) fast = false;  // float -> narrow integer: generic kernel
+  if (fast && s.type == SINK_MEASURE && s.agg == AGGR_AVG_FLOAT && !avg_hot_shape(f)) fast = false;
   if (fast && f.idx && virtual_iota(device, indexVector, n, false)) f.idx = nullptr;  // rows = position
   // root outputs of the hot shape are held back and fused with their siblings (same index vector)
   if (fast && (s.type == SINK_DIM || s.type == SINK_MEASURE) && defer_transform(device, stream, f, s, n, p.a.length, decoded)) return n;

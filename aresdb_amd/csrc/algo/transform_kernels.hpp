@@ -728,6 +728,7 @@ __device__ __forceinline__ void store_tile(const FastOperands &f, const SinkD &s
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           if (!r[j].ok) o[j] = s.identity;
+          else if (s.agg == AGGR_AVG_FLOAT) o[j] = (1ull << 32) | f_bits(avg_measure_float(s.dtype, r[j], f.rk));  // {average, count 1}
           else if (s.dtype == Float64) o[j] = static_cast<uint64_t>(__double_as_longlong(to_double32(r[j], f.rk)));
           else o[j] = static_cast<uint64_t>(f.rk == K_F32 ? static_cast<int64_t>(bits_f(r[j].bits))
                                             : f.rk == K_I32 ? static_cast<int64_t>(static_cast<int32_t>(r[j].bits))

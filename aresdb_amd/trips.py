@@ -203,3 +203,48 @@ def compare(fetched, expected, count=False):
             why = f"{len(bad)} values differ (first: code {got_code[go][bad[0]]} got {got_val[go][bad[0]]!r} expected {want_val[wo][bad[0]]!r})"
     return {"status": "ok" if why is None else "MISMATCH: " + why, "groups": int(len(got_code)), "expected_groups": int(len(want_code)),
             "merged_by_32bit_hash": merged}
+
+
+def exact_means(batches, time_range=TIME_RANGE):
+    """Exact AVG(fare) per (hour, city): numpy (code, mean, valid_rows, abs_sum) — valid_rows counts the rows whose fare is not
+    null (the count AVG_FLOAT carries), abs_sum = sum|fare| over them (aresdb_amd/check.py: exact_means, compare_means)."""
+    dev = batches[0]["fare"].blob.device
+    space, salt = _R_HOUR * _R_CITY, 64
+    acc = torch.zeros(space * salt, dtype=torch.float64, device=dev)
+    mag = torch.zeros(space * salt, dtype=torch.float64, device=dev)
+    cnt = torch.zeros(space * salt, dtype=torch.int64, device=dev)
+    rows_of = torch.zeros(space * salt, dtype=torch.int64, device=dev)
+    offset = 0
+    for b in batches:
+        ts, city, st, fare = (column_values(b[k]) for k in ("request_at", "city_id", "status", "fare"))
+        ok = {k: _valid(b[k]) for k in b}
+        keep = (ts >= time_range[0]) & (ts < time_range[1]) & (st == COMPLETED)
+        for k in ("request_at", "status"):
+            if ok[k] is not None:
+                keep &= ok[k]
+        c = city.to(torch.int64) & 0xFFFF
+        if ok["city_id"] is not None:
+            c = torch.where(ok["city_id"], c, torch.full_like(c, CITIES))
+        code = torch.div(ts, 3600, rounding_mode="floor").to(torch.int64) * _R_CITY + c
+        mm = fare.to(torch.float64)
+        if ok["fare"] is not None:
+            mm = torch.where(ok["fare"], mm, torch.zeros_like(mm))
+        rows = torch.arange(offset, offset + code.numel(), dtype=torch.int64, device=dev)[keep]
+        idx = code[keep] * salt + rows % salt
+        acc.index_add_(0, idx, mm[keep])
+        mag.index_add_(0, idx, mm[keep].abs())
+        cnt.index_add_(0, idx, torch.ones_like(idx) if ok["fare"] is None else ok["fare"][keep].to(torch.int64))
+        rows_of.index_add_(0, idx, torch.ones_like(idx))
+        offset += code.numel()
+        del ts, city, st, fare, keep, c, code, mm, rows, idx
+    acc, mag, cnt, rows_of = (x.view(space, salt).sum(1) for x in (acc, mag, cnt, rows_of))
+    live = torch.nonzero(rows_of > 0).reshape(-1)
+    mean = acc[live] / cnt[live].clamp(min=1).to(torch.float64)
+    return live.cpu().numpy(), mean.cpu().numpy(), cnt[live].cpu().numpy(), mag[live].cpu().numpy()
+
+
+def fetched_codes(fetched):
+    """dense (hour, city) codes of NativeQuery.fetch()'s rows, as compare() forms them"""
+    dims, valids, _ = fetched
+    g_ok = np.frombuffer(valids[1], np.uint8).astype(bool)
+    return (np.frombuffer(dims[0], np.uint32).astype(np.int64) // 3600) * _R_CITY + np.where(g_ok, np.frombuffer(dims[1], np.uint16).astype(np.int64), CITIES)

@@ -407,6 +407,66 @@ def sort_float_leg(be, dev, rows, batch_rows=1 << 26, steps=3):
              "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}]
 
 
+def sort_avg_legs(be, dev, which, rows, batch_rows=1 << 26, steps=3):
+    """c3sortavg: AVG(m) over the C3 shard with full-mantissa measures (sort_float_leg's shard and query, AGGR_AVG_FLOAT: the Go
+    compiler's 8-byte {f32 average, u32 count} measure, always through Sort + Reduce).  tripsavg: AVG(fare) over the trips-shaped
+    shard (67 k groups, a Uint16 slot, a Uint8 filter column).  Rows must come in ascending order of their 64-bit row hash (C3),
+    every key's count must be exact and its average within 1e-4 * sum|x| / count of the exact group-by (check.compare_means).
+    ARES_SR_SCAN_FED=0 in the environment gives the same legs on the wide layout over materialised rows."""
+    import dataclasses
+    from aresdb_amd import check, trips
+    if which == "c3sortavg":
+        shard = workload.c3_shard(rows, batch_rows, seed=1, device=dev, quantised=False)
+        names, last = [n for n, _ in workload.C3_COLUMNS], "m"
+        plan = dataclasses.replace(queries.c3_plan(use_hash_reduction=False), agg=abi.AGGR_AVG_FLOAT)
+        bytes_per_row = 5 * (4 + 1 / 8)
+    else:
+        shard = trips.trips_shard(rows, batch_rows, seed=11, device=dev)
+        names, last = [n for n, _ in trips.COLUMNS], "fare"
+        plan = dataclasses.replace(trips.trips_plan(), agg=abi.AGGR_AVG_FLOAT, use_hash_reduction=False)
+        bytes_per_row = 4 + 2 + 1 + 4 + 4 / 8
+    vps = [({k: rc.vp for k, rc in b.items()}, b[last].length) for b in shard]
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    packed = None
+    def run():
+        nonlocal packed
+        q = NativeQuery(be, plan, names, streams=streams)
+        if packed is None:
+            packed = q.pack_batches(vps)
+        q.run_batches(packed)
+        return q
+    compiles = -1
+    for _ in range(4):  # priming passes: the shape's scan is compiled in the background — until a pass builds nothing new
+        run().release()
+        state = be.rtc_wait()
+        if state is None or state["compiles"] == compiles:
+            break
+        compiles = state["compiles"]
+    passes = []
+    for _ in range(steps):
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        run().release()
+        torch.cuda.synchronize(); passes.append((time.perf_counter() - t0) * 1e3)
+    dt = sum(passes) / len(passes) * 1e-3
+    be.profiler_enable(True)
+    q = run(); torch.cuda.synchronize()
+    kernels = be.profiler_report(); be.profiler_enable(False)
+    groups = q.result_size
+    fetched = q.fetch()
+    if which == "c3sortavg":
+        rep = check.compare_mean_result(fetched, check.exact_means(shard))
+    else:
+        why = check.compare_means(trips.fetched_codes(fetched), fetched[2], trips.exact_means(shard))
+        rep = {"status": "ok" if why is None else "MISMATCH: " + why}
+    q.release()
+    return [{"config": "c3-sort-avg" if which == "c3sortavg" else "trips-shaped", "query": "AVG(%s) via Sort+Reduce" % last,
+             "scan_fed": os.environ.get("ARES_SR_SCAN_FED", "1") != "0", "rows": rows, "batches": len(vps), "batch_rows": batch_rows, "groups": groups,
+             "counts_exact_and_averages_rel_1e-4": rep["status"], "groups_without_a_valid_measure": rep.get("groups_without_a_valid_measure"),
+             "ms_per_step": dt * 1e3, "ms_per_pass": passes, "ms_per_1e9_rows": dt * 1e3 * 1e9 / rows, "rows_per_s": rows / dt,
+             "algorithmic_bytes_per_row": bytes_per_row, "kernel_ms_per_step": sum(ms for c, ms in kernels.values()),
+             "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}]
+
+
 def hll(be, dev, rows, groups, users, batches=2):
     """countdistincthll(user) group by g: `batches` batches of `rows` rows through the C++ driver."""
     from aresdb_amd.executor import Unary
@@ -491,6 +551,8 @@ def main():
     for leg in ("c3int64", "uuid"):
         if leg in which: res += wide_key_legs(be, dev, leg, int(float(os.environ.get("WIDE_ROWS", str(1 << 28)))))
     if "c3sortfloat" in which: res += sort_float_leg(be, dev, int(float(os.environ.get("SORT_FLOAT_ROWS", "1e9"))))
+    for leg in ("c3sortavg", "tripsavg"):
+        if leg in which: res += sort_avg_legs(be, dev, leg, int(float(os.environ.get("SORT_AVG_ROWS", "1e9"))))
     if "hll" in which:
         res += hll(be, dev, 1 << 25, 1000, 5_000_000) + hll(be, dev, 1 << 25, 4, 50_000_000) + hll(be, dev, 1 << 25, 100, 50_000_000, batches=4)
     if "geo" in which: res += geo(be, dev, 1 << 24, 100, 20) + geo(be, dev, 1 << 22, 250, 400)
