@@ -630,9 +630,11 @@ class GeoCase:
     """Random polygons (one or two rings each) x random points through GeoBatchIntersects and
     WriteGeoShapeDim: non-identity index vectors, null points, RecordID vectors that must be
     compacted alongside, up to 200 shapes (shape numbers >= 128 wrap negative in the reference's
-    int8 predicate iterator), points read from the main table or through a join."""
+    int8 predicate iterator; `shapes` takes up to 256, all eight predicate words), points read from
+    the main table or through a join.  `max_ring` lengthens the rings from 3 - 8 vertices to
+    3 - max_ring, past the 64 edges one wavefront walks at a time."""
 
-    def __init__(self, seed, rows=None, shapes=None, foreign_points=None):
+    def __init__(self, seed, rows=None, shapes=None, foreign_points=None, max_ring=None):
         rng = np.random.default_rng(seed)
         self.seed = seed
         self.num_shapes = shapes or int(rng.choice([1, 3, 33, 70, 200]))
@@ -641,7 +643,7 @@ class GeoCase:
         for sh in range(self.num_shapes):
             cx, cy = rng.uniform(-50, 50, 2)
             for ring in range(int(rng.integers(1, 3))):
-                k = int(rng.integers(3, 9))
+                k = int(rng.integers(3, 9 if max_ring is None else max_ring + 1))
                 ang = np.sort(rng.uniform(0, 2 * np.pi, k))
                 rad = rng.uniform(2, 30) / (1 + 2 * ring)
                 ys = (cy + rad * np.sin(ang)).astype(np.float32)

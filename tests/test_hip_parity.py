@@ -296,10 +296,14 @@ def test_geo_intersects(seed):
     cases.assert_same(c.run(hip()), c.run(H.oracle_backend()), repr(c))
 
 
-@pytest.mark.parametrize("seed,rows,shapes,foreign", [(900, 150000, 200, False), (901, 100000, 33, True),
-                                                      (902, 300000, 1, False), (903, 70000, 70, False)])
-def test_geo_intersects_multi_tile(seed, rows, shapes, foreign):
-    c = cases.GeoCase(seed, rows=rows, shapes=shapes, foreign_points=foreign)
+@pytest.mark.parametrize("seed,rows,shapes,foreign,max_ring", [
+    (900, 150000, 200, False, None), (901, 100000, 33, True, None), (902, 300000, 1, False, None), (903, 70000, 70, False, None),
+    # rings of up to 150 vertices (three 64-edge chunks) and 256 shapes (all eight predicate words)
+    (904, 6000, 256, False, 150), (905, 5000, 256, True, 150), (906, 20000, 3, False, 150), (907, 9000, 70, True, 150)],
+    ids=["900-150000-200-False", "901-100000-33-True", "902-300000-1-False", "903-70000-70-False",
+         "904-long-rings-256", "905-long-rings-256-joined", "906-long-rings-3", "907-long-rings-70-joined"])
+def test_geo_intersects_multi_tile(seed, rows, shapes, foreign, max_ring):
+    c = cases.GeoCase(seed, rows=rows, shapes=shapes, foreign_points=foreign, max_ring=max_ring)
     cases.assert_same(c.run(hip()), c.run(H.oracle_backend()), repr(c))
 
 

@@ -56,9 +56,15 @@ def test_hyperloglog_dense_groups():
     cases.assert_same(r, c.run(H.ref_backend()), repr(c))
 
 
-@pytest.mark.parametrize("seed", range(60))
-def test_geo_intersects(seed):
-    c = cases.GeoCase(seed)
+# (seed, GeoCase arguments): the seeded cases, then long rings (up to 150 vertices) and 256 shapes, kept small for the host build
+GEO_CASES = [(seed, {}) for seed in range(60)] + [
+    (904, dict(rows=700, shapes=256, foreign_points=False, max_ring=150)), (905, dict(rows=600, shapes=256, foreign_points=True, max_ring=150)),
+    (906, dict(rows=3000, shapes=3, foreign_points=False, max_ring=150)), (907, dict(rows=1500, shapes=70, foreign_points=True, max_ring=150))]
+
+
+@pytest.mark.parametrize("seed,kw", GEO_CASES, ids=[str(s) for s, _ in GEO_CASES])
+def test_geo_intersects(seed, kw):
+    c = cases.GeoCase(seed, **kw)
     r = c.run(H.oracle_backend())
     cases.assert_same(r, c.run(H.ref_backend()), repr(c))
 
