@@ -516,7 +516,7 @@ int hash_reduce_lds(int device, const DimensionVector &inputKeys, const uint8_t 
     // for this vector shape (hr_rtc.hip), instead of the adaptive kernel's scattered DIRECT-mode stores
     RtcKernel lean;
     if (all4 && grouped && rows > 0 && start >= lean_min_groups() && (a.width == 4 || a.width == 8) && rtc_scan_available())
-      lean = rtc_vector_scan_lookup(device, L.numDims, a.width, partBits);
+      lean = rtc_lookup(device, rtc_spec_vector_scan(L.numDims, a.width, partBits));
     const int streams = (all4 && rows > 0) ? (lean ? rtc_scan_grid(rows) : grid_for(rows)) : 0;
     const int rwB = (a.width == 8 || lean) ? 4 : 3;
     Regions r;
@@ -526,11 +526,11 @@ int hash_reduce_lds(int device, const DimensionVector &inputKeys, const uint8_t 
     ws.prevRanges = grouped ? prev.ranges.get() : nullptr;
     ws.outRanges = outRanges;
     // the specialised merge for these records (it writes every partition's range entry itself)
-    RtcKernel leanMerge = lean ? rtc_vector_merge_lookup(device, L.numDims, a.width, partBits, a) : nullptr;
+    RtcKernel leanMerge = lean ? rtc_lookup(device, rtc_spec_vector_merge(L.numDims, a.width, partBits, a)) : nullptr;
     if (outRanges && !leanMerge) hip_check(hipMemsetAsync(outRanges, 0, kRangesBytes, stream), "hipMemsetAsync");
     if (lean) {
-      rtc_vector_scan_launch(lean, inputKeys.DimValues, capacity, inputValues, L.numDims, a.width, static_cast<uint32_t>(start), rows,
-                             ws, stream);
+      rtc_vector_scan_launch(lean, RTC_VECTOR_SCAN, inputKeys.DimValues, capacity, inputValues + static_cast<size_t>(a.width) * start,
+                             L.numDims, nullptr, static_cast<uint32_t>(start), rows, ws, stream);
     } else if (all4) {
       if (rows > 0) {
 #define ARES_HR_CASE(ND)                                                                                             \
@@ -617,7 +617,6 @@ int hash_reduce_lds(int device, const DimensionVector &inputKeys, const uint8_t 
   return static_cast<int>(res.groups);
 }
 
-
 // The fused pipeline for an already built plan (shared by the extension entry point and by the
 // in-ABI fusion of pending transforms into HashReduce, transform.hip).  Returns the number of groups
 // or -1 when a region overflowed.
@@ -679,7 +678,8 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   bool known = prevSize > 0;
   const bool rtc = batchRows > 0 && rtc_scan_available();
   if (rtc && prevSize == 0) {
-    shape = std::hash<std::string>()(rtc_scan_source(plan, nd, 0));
+    const RtcSpec spec = rtc_spec_scan(plan, nd, 0, false);  // (only equality of shapes matters: the hash of its bytes)
+    shape = std::hash<std::string>()(std::string(reinterpret_cast<const char *>(&spec), sizeof(spec)));
     std::lock_guard<std::mutex> lock(g_shapeMutex);
     auto it = g_firstBatchGroups.find(shape);
     if (it != g_firstBatchGroups.end()) {
@@ -689,6 +689,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   }
   const int chunkTiles = compact_enabled() ? rtc_compact_chunk_tiles(batchRows, partBits) : 0;
   const bool compact = chunkTiles > 0;
+  const RtcKind leanKind = compact ? RTC_SCAN_COMPACT : RTC_SCAN_LINES16;
   RtcKernel lean, table, tableMerge, narrowMerge;
   SlowScope slowWhole("fused_hash_reduce_run");
   // (ARES_LEAN_MIN_GROUPS=0 — tests — sends every batch, known shape or not, to the DIRECT kernels)
@@ -696,8 +697,8 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   // (a narrow shape nobody has seen has no adaptive generic kernel to find its cardinality out with: the TABLE scan takes
   // it — right for any number of groups, rows that find the table full travel alone — and the next first batch knows)
   const bool wantTable = rtc && !wantLean && (known || narrow);
-  if (wantLean) lean = rtc_scan_lookup(device, plan, nd, partBits, compact);
-  else if (wantTable) table = rtc_table_scan_lookup(device, plan, nd, partBits, a, widen);
+  if (wantLean) lean = rtc_lookup(device, rtc_spec_scan(plan, nd, partBits, compact));
+  else if (wantTable) table = rtc_lookup(device, rtc_spec_table_scan(plan, nd, partBits, a, widen));
   // ---- table image (see "table images" above): 2 = the merge starts from the image the previous call left with the input
   // vectors; 1 = the ordinary specialised merge, which leaves an image for the next call.  DIRECT-mode batches only.
   int imageMode = 0;
@@ -707,7 +708,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   if (image_enabled() && wantLean && lean) {
     if (found && prev.image) imageMode = 2;
     else if (prevSize == 0 || grouped) imageMode = 1;
-    if (imageMode) imageMerge = rtc_merge_lookup(device, plan, nd, partBits, a, widen, compact, false, false, imageMode);
+    if (imageMode) imageMerge = rtc_lookup(device, rtc_spec_merge(plan, nd, partBits, a, widen, compact, false, imageMode));
     if (!imageMerge) imageMode = 0;  // (being compiled in the background: the ordinary kernels this time)
   }
   if (imageMode == 2) {
@@ -742,8 +743,8 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
               narrow ? 1 : 0, imageMode, knownOut);
   }
   if (narrow && !imageMode) {  // (both kernels are asked for before the call is declined: one round of background compilation, not two)
-    narrowMerge = rtc_merge_lookup(device, plan, nd, partBits, a, widen, wantLean && compact, false,
-                                   /*regionA=*/wantTable || (prevSize > 0 && !grouped));
+    narrowMerge = rtc_lookup(device, rtc_spec_merge(plan, nd, partBits, a, widen, wantLean && compact,
+                                                    /*regionA=*/wantTable || (prevSize > 0 && !grouped)));
     if (!narrowMerge) return kFusedUnavailable;  // still being compiled (or a shape the generator declines)
   }
   if (narrow && !(wantLean ? lean : table)) return kFusedUnavailable;
@@ -753,7 +754,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
     // not grouped by partition (re-partitioned below by the layout-generic kernel)
     const bool prevToA = narrow && prevSize > 0 && !grouped && imageMode != 2;
     if (narrow && !imageMode) {
-      narrowMerge = rtc_merge_lookup(device, plan, nd, partBits, a, widen, lean && compact, false, /*regionA=*/table || prevToA);
+      narrowMerge = rtc_lookup(device, rtc_spec_merge(plan, nd, partBits, a, widen, lean && compact, /*regionA=*/table || prevToA));
       if (!narrowMerge) return launched ? -1 : kFusedUnavailable;
       if (table) tableMerge = narrowMerge;
     }
@@ -779,7 +780,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
     // the specialised merge reads region B and grouped previous results only
     RtcKernel leanMerge = imageMode ? imageMerge
                           : narrow  ? (lean ? narrowMerge : nullptr)
-                          : (lean && (prevSize == 0 || grouped)) ? rtc_merge_lookup(device, plan, nd, partBits, a, widen, compact) : nullptr;
+                          : (lean && (prevSize == 0 || grouped)) ? rtc_lookup(device, rtc_spec_merge(plan, nd, partBits, a, widen, compact)) : nullptr;
     RtcImageArgs imageArgs{nullptr, nullptr, nullptr, nullptr, 0u};
     if (imageMode) {
       imageArgs.in = imageMode == 2 ? prev.image.get() : nullptr;
@@ -808,9 +809,9 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
                     prevKeys.DimValues, prevCapacity, prevValues, 0u, a, prevSize, wsPrev, 0);                         \
     }                                                                                                                  \
     if (batchRows > 0 && lean)                                                                                         \
-      rtc_scan_launch(lean, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);                             \
+      rtc_scan_launch(lean, leanKind, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);                   \
     else if (batchRows > 0 && table)                                                                                   \
-      rtc_table_scan_launch(table, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);                      \
+      rtc_scan_launch(table, RTC_SCAN_TABLE, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);            \
     else if (batchRows > 0)                                                                                            \
       ARES_LAUNCH("hr_fused_scan_kernel", hr_fused_scan_kernel<ND>, streams, kThreads, stream, plan,                   \
                   static_cast<uint32_t>(prevSize), a, batchRows, ws);                                                  \
@@ -830,8 +831,8 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
     switch (nd) {
       ARES_FUSED_CASE(1) ARES_FUSED_CASE(2) ARES_FUSED_CASE(3) ARES_FUSED_CASE(4)
       default:  // five to eight dimensions: the generated kernels only (the plan counts as narrow: both were looked up above)
-        if (batchRows > 0 && lean) rtc_scan_launch(lean, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
-        else if (batchRows > 0 && table) rtc_table_scan_launch(table, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
+        if (batchRows > 0 && lean) rtc_scan_launch(lean, leanKind, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
+        else if (batchRows > 0 && table) rtc_scan_launch(table, RTC_SCAN_TABLE, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
         rtc_merge_launch(leanMerge ? leanMerge : tableMerge, plan, prevKeys.DimValues, prevCapacity, prevValues, static_cast<uint32_t>(prevSize),
                          outKeys.DimValues, outCapacity, outValues, ws, stream, imagePtr, result_slot());
         break;
@@ -891,10 +892,10 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   if (shape && !lean && !table) {
     // the next first batch of this shape takes the specialised kernels: have them built now (in the background)
     if (static_cast<int>(res.groups) >= lean_min_groups()) {
-      (void)rtc_scan_lookup(device, plan, nd, partBits, compact);
-      (void)rtc_merge_lookup(device, plan, nd, partBits, a, widen, compact);
+      (void)rtc_lookup(device, rtc_spec_scan(plan, nd, partBits, compact));
+      (void)rtc_lookup(device, rtc_spec_merge(plan, nd, partBits, a, widen, compact));
     } else {
-      (void)rtc_table_scan_lookup(device, plan, nd, partBits, a, widen);
+      (void)rtc_lookup(device, rtc_spec_table_scan(plan, nd, partBits, a, widen));
     }
   }
   if (outRanges) {
@@ -915,7 +916,6 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   }
   return static_cast<int>(res.groups);
 }
-
 
 // ---- fused extension: host side ---------------------------------------------------------------------
 namespace {

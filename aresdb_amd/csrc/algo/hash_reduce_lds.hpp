@@ -82,8 +82,8 @@ inline bool fused_plan_narrow(const FusedPlanD &p, int nd) {
 
 // ---- building a plan ------------------------------------------------------------------------------------------------
 // One copy of each decision for everybody who writes a FusedPlanD: the two fusions over a stream's pending work
-// (transform.hip), the fused extension (hash_reduce_lds.hip) and the vector-sourced launchers (hr_rtc.hip).  The struct is
-// memset to zero first; shape_key and the generators read it field by field.
+// (transform.hip), the fused extension (hash_reduce_lds.hip) and the vector-sourced launcher (hr_rtc.hip).  The struct is
+// memset to zero first; the spec makers (hr_rtc_gen.hpp) and the launches read it field by field.
 inline FusedColumn fused_column_of(const FastOperands &f) { return FusedColumn{f.vals, f.nulls, f.bitOff, static_cast<uint32_t>(f.step ? f.step : 4)}; }
 // the expression without what belongs to one launch (the column lives in its slot, the rows come from the scan)
 inline FastOperands fused_strip(FastOperands f) {

@@ -485,7 +485,7 @@ int hll_preagg_batch(const DimensionVector &prev, const DimensionVector &cur, ui
   const DimLayoutD L = make_dim_layout(cur.NumDimsPerDimWidth);
   int widths[kFusedDims];
   for (int d = 0; d < L.numDims; d++) widths[d] = L.width[d];
-  const RtcKernel scan = rtc_hll_scan_lookup(device, L.numDims, widths, kPreaggPartBits);
+  const RtcKernel scan = rtc_lookup(device, rtc_spec_hll_scan(L.numDims, widths, kPreaggPartBits));
   if (!scan) return -1;  // (being compiled in the background)
 
   const int streams = rtc_scan_grid(n);
@@ -523,7 +523,7 @@ int hll_preagg_batch(const DimensionVector &prev, const DimensionVector &cur, ui
   ws.partBits = kPreaggPartBits;
   ws.lineRecords = 8;
   ws.rowBase = static_cast<uint32_t>(P);
-  rtc_hll_scan_launch(scan, prev.DimValues, capacity, curValues, L.numDims, widths, static_cast<uint32_t>(P), n, ws, stream);
+  rtc_vector_scan_launch(scan, RTC_HLL_SCAN, prev.DimValues, capacity, curValues, L.numDims, widths, static_cast<uint32_t>(P), n, ws, stream);
   DedupParams dp;
   dp.rec = rec;
   dp.counts = counts;

@@ -1144,7 +1144,7 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
   if (static_cast<int64_t>(prevSize) > static_cast<int64_t>(numParts) * tableGroups * 9 / 10) return kFusedUnavailable;
   const DimLayoutD L = make_dim_layout(in.NumDimsPerDimWidth);
   if (L.numDims != nd) return kFusedUnavailable;
-  RtcKernel scan = rtc_sort_scan_lookup(device, plan, nd, partBits);
+  RtcKernel scan = rtc_lookup(device, rtc_spec_sort_scan(plan, nd, partBits));
   if (!scan) return kFusedUnavailable;  // being compiled in the background (or a shape the generator declines)
 
   // ---- workspace: [cursors A | flags][counts B][partition counts][region A][region B][staging]
@@ -1215,7 +1215,7 @@ int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool const
     const int grid = static_cast<int>(std::min<int64_t>((static_cast<int64_t>(prevSize) + 255) / 256, 256 * 8));
     ARES_LAUNCH("sr_prev_kernel", sr_prev_kernel, grid, 256, stream, m, L, ws.recA);
   }
-  rtc_sort_scan_launch(scan, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
+  rtc_scan_launch(scan, RTC_SCAN_SORT64, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
   m.phases = merge_phase_stamps(numParts, stream);
   const bool flt = float_agg(a);
   if (vw == 8) {
@@ -1287,7 +1287,7 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
   const int numParts = 1 << partBits;
   if (static_cast<int64_t>(length) > static_cast<int64_t>(numParts) * tableGroups * 7 / 10) return decline("more rows than the tables take");  // (all rows may be groups)
   const int pb1 = partBits < 9 ? partBits : 9, numParts1 = 1 << pb1;
-  RtcKernel scan = rtc_sort_vector_scan_lookup(device, nd, widths, pb1);
+  RtcKernel scan = rtc_lookup(device, rtc_spec_sort_vector_scan(nd, widths, pb1));
   if (!scan) return decline("scan kernel not available (yet)");  // being compiled in the background
 
   int prevSize = 0;
@@ -1375,7 +1375,10 @@ static int sort_reduce_vectors_run(int device, int length, const DimensionVector
     ws.partBits = pb1;
     ws.lineRecords = 8;
     ws.rowBase = static_cast<uint32_t>(prevSize);
-    rtc_sort_vector_scan_launch(scan, in.DimValues, static_cast<size_t>(in.VectorCapacity), inValues, nd, widths, static_cast<uint32_t>(prevSize), batchRows, partBits, spread, ws, stream);
+    // (8-byte values: read at the 4-byte stride and ignored)
+    rtc_vector_scan_launch(scan, RTC_SORT_VECTOR_SCAN, in.DimValues, static_cast<size_t>(in.VectorCapacity),
+                           reinterpret_cast<const uint32_t *>(inValues) + prevSize, nd, widths, static_cast<uint32_t>(prevSize), batchRows, ws,
+                           stream, partBits, spread);
     SplitArgs sp;
     memset(&sp, 0, sizeof(sp));
     sp.rec1 = rec1;

@@ -1,4 +1,4 @@
-// The Sort + Reduce scan (hr_rtc.hip, SCAN_SORT64) generated for AVG_FLOAT next to its SUM_FLOAT-into-float64 sibling of the
+// The Sort + Reduce scan (hr_rtc_gen.hip, RTC_SCAN_SORT64) generated for AVG_FLOAT next to its SUM_FLOAT-into-float64 sibling of the
 // same shape — the C3 plan and the narrow trips plan of tools/rtc_check.cpp — compiled for gfx950 (no GPU needed):
 //   tools/bin/rtc_check_avg [out-prefix]   writes <prefix>_<tag>.hip and <prefix>_<tag>.co
 // Links against aresdb_amd/lib/libalgorithm.so like rtc_check.
@@ -11,33 +11,12 @@
 #include <string>
 #include <vector>
 
-#include "hash_reduce_lds.hpp"
-#include "hr_kernels.hpp"
-#include "hr_rtc.hpp"
+#include "rtc_shapes.hpp"
 
-using namespace ares;
-
-static FastOperands col(int akind) {
-  FastOperands f;
-  memset(&f, 0, sizeof(f));
-  f.akind = akind; f.arity = 1; f.functor = Noop; f.I = akind; f.rk = akind; f.bkind = akind;
-  return f;
-}
+using namespace rtc_shapes;
 
 int main(int argc, char **argv) {
-  // C3: dims [Floor(ts, 3600), d1, d2, d3], filter d1 < 90, a Float32 measure column into an 8-byte Float64-typed measure
-  FusedPlanD p;
-  memset(&p, 0, sizeof(p));
-  p.numCols = 5;
-  for (int c = 0; c < 5; c++) { p.cols[c].vals = reinterpret_cast<const uint32_t *>(0x1000); p.cols[c].nulls = reinterpret_cast<const uint8_t *>(0x2000); }
-  p.numFilters = 1;
-  p.filters[0].f = col(K_U32); p.filters[0].f.arity = 2; p.filters[0].f.functor = LessThan; p.filters[0].f.bkind = K_I32;
-  p.filters[0].f.bbits = 90; p.filters[0].f.bok = 1; p.filters[0].col = 1; p.filters[0].outKind = K_BOOL;
-  p.dims[0].f = col(K_U32); p.dims[0].f.arity = 2; p.dims[0].f.functor = Floor; p.dims[0].f.bkind = K_I32; p.dims[0].f.bbits = 3600;
-  p.dims[0].f.bok = 1; p.dims[0].f.divLike = 1; p.dims[0].col = 0; p.dims[0].outKind = K_U32;
-  for (int d = 1; d < 4; d++) { p.dims[d].f = col(K_U32); p.dims[d].col = d; p.dims[d].outKind = K_U32; }
-  p.measure.f = col(K_F32); p.measure.col = 4; p.measure.outKind = K_F32;
-  p.measureDtype = Float64; p.measureWidth = 8; p.identity = 0;
+  const FusedPlanD p = c3_plan();
   // trips: dims [Floor(request_at, 3600) Uint32, city_id Uint16 -> 2-byte slot], fare Float32, filters request_at >= / <,
   // status == k on a Uint8 column
   FusedPlanD t = p;
@@ -53,7 +32,8 @@ int main(int argc, char **argv) {
 
   const std::string prefix = argc > 1 ? argv[1] : "/tmp/sr_avg_rtc";
   const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics"};
-  auto build = [&](const std::string &src, const std::string &tag, const char *what) -> int {
+  auto build = [&](const Shape &shape, const std::string &tag, const char *what) -> int {
+    const std::string src = source(shape);
     if (src.empty()) { printf("%s: unsupported plan\n", what); return 2; }
     std::ofstream(prefix + tag + ".hip") << src;
     hiprtcProgram prog;
@@ -69,34 +49,34 @@ int main(int argc, char **argv) {
     return 0;
   };
   auto averaged = [](FusedPlanD q) { q.measureAvg = 1; return q; };
-  if (int rc = build(rtc_sort_scan_source(p, 4, 9), "_c3_fsum8", "C3 sort scan (SUM_FLOAT into 8 bytes)")) return rc;
-  if (int rc = build(rtc_sort_scan_source(averaged(p), 4, 9), "_c3_avg", "C3 sort scan (AVG_FLOAT)")) return rc;
-  if (int rc = build(rtc_sort_scan_source(t, 2, 9), "_trips_fsum8", "trips sort scan (SUM_FLOAT into 8 bytes)")) return rc;
-  if (int rc = build(rtc_sort_scan_source(averaged(t), 2, 9), "_trips_avg", "trips sort scan (AVG_FLOAT)")) return rc;
+  if (int rc = build(sort_scan(p, 4, 9), "_c3_fsum8", "C3 sort scan (SUM_FLOAT into 8 bytes)")) return rc;
+  if (int rc = build(sort_scan(averaged(p), 4, 9), "_c3_avg", "C3 sort scan (AVG_FLOAT)")) return rc;
+  if (int rc = build(sort_scan(t, 2, 9), "_trips_fsum8", "trips sort scan (SUM_FLOAT into 8 bytes)")) return rc;
+  if (int rc = build(sort_scan(averaged(t), 2, 9), "_trips_avg", "trips sort scan (AVG_FLOAT)")) return rc;
   // the variant is a different source: the null bit travels in the row word, a null measure is not a zero
-  if (rtc_sort_scan_source(averaged(p), 4, 9) == rtc_sort_scan_source(p, 4, 9)) { puts("AVG_FLOAT must not share SUM_FLOAT's source"); return 20; }
-  if (rtc_sort_scan_source(averaged(p), 4, 9).find("0x80000000u") == std::string::npos) { puts("no null bit in the AVG source"); return 21; }
-  if (rtc_sort_scan_source(p, 4, 9).find("0x80000000u") != std::string::npos) { puts("the null bit leaks into the SUM source"); return 22; }
+  if (source(sort_scan(averaged(p), 4, 9)) == source(sort_scan(p, 4, 9))) { puts("AVG_FLOAT must not share SUM_FLOAT's source"); return 20; }
+  if (source(sort_scan(averaged(p), 4, 9)).find("0x80000000u") == std::string::npos) { puts("no null bit in the AVG source"); return 21; }
+  if (source(sort_scan(p, 4, 9)).find("0x80000000u") != std::string::npos) { puts("the null bit leaks into the SUM source"); return 22; }
   {  // the conversions of avg_measure_float: integer columns (and column + constant) into Float64- and Int64-typed measures
     FusedPlanD i = averaged(p);
     i.measure.f = col(K_I32); i.measure.outKind = K_F32;
-    if (int rc = build(rtc_sort_scan_source(i, 4, 9), "_c3_avg_i32", "C3 sort scan (AVG of an Int32 column)")) return rc;
+    if (int rc = build(sort_scan(i, 4, 9), "_c3_avg_i32", "C3 sort scan (AVG of an Int32 column)")) return rc;
     i.measure.f = col(K_U32); i.measure.f.arity = 2; i.measure.f.functor = Plus; i.measure.f.bkind = K_I32; i.measure.f.bbits = 5; i.measure.f.bok = 1;
-    if (int rc = build(rtc_sort_scan_source(i, 4, 9), "_c3_avg_u32", "C3 sort scan (AVG of a Uint32 column + 5)")) return rc;
+    if (int rc = build(sort_scan(i, 4, 9), "_c3_avg_u32", "C3 sort scan (AVG of a Uint32 column + 5)")) return rc;
     i.measureDtype = Int64;
-    if (int rc = build(rtc_sort_scan_source(i, 4, 9), "_c3_avg_u32_i64", "C3 sort scan (AVG into an Int64-typed measure)")) return rc;
+    if (int rc = build(sort_scan(i, 4, 9), "_c3_avg_u32_i64", "C3 sort scan (AVG into an Int64-typed measure)")) return rc;
     FusedPlanD fx = averaged(p);
     fx.measure.f.arity = 2; fx.measure.f.functor = Multiply; fx.measure.f.bkind = K_F32; fx.measure.f.bbits = 0x3fc00000u; fx.measure.f.bok = 1;
-    if (int rc = build(rtc_sort_scan_source(fx, 4, 9), "_c3_avg_fexpr", "C3 sort scan (AVG of m * 1.5)")) return rc;
+    if (int rc = build(sort_scan(fx, 4, 9), "_c3_avg_fexpr", "C3 sort scan (AVG of m * 1.5)")) return rc;
   }
   {  // declined: a constant AVG measure, a 4-byte AVG measure, and AVG on HashReduce's scans
     FusedPlanD c = averaged(p);
     c.numCols = 4; c.measure.col = -1;
-    if (!rtc_sort_scan_source(c, 4, 9).empty()) { puts("a constant AVG measure must be declined"); return 23; }
+    if (!source(sort_scan(c, 4, 9)).empty()) { puts("a constant AVG measure must be declined"); return 23; }
     FusedPlanD w4 = averaged(p);
     w4.measureDtype = Float32; w4.measureWidth = 4;
-    if (!rtc_sort_scan_source(w4, 4, 9).empty()) { puts("a 4-byte AVG measure must be declined"); return 24; }
-    if (!rtc_scan_source(averaged(p), 4, 9, false).empty() || !rtc_scan_source(averaged(p), 4, 9, true).empty()) { puts("HashReduce's scans must decline AVG"); return 25; }
+    if (!source(sort_scan(w4, 4, 9)).empty()) { puts("a 4-byte AVG measure must be declined"); return 24; }
+    if (!source(scan(averaged(p), 4, 9, false)).empty() || !source(scan(averaged(p), 4, 9, true)).empty()) { puts("HashReduce's scans must decline AVG"); return 25; }
   }
   return 0;
 }
