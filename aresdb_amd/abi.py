@@ -139,6 +139,18 @@ class GeoShapeBatch(C.Structure):
     _fields_ = [("LatLongs", C.c_void_p), ("TotalNumPoints", C.c_int32), ("TotalWords", C.c_uint8)]
 
 
+class FusedExpr(C.Structure):
+    """AresFusedExpr (include/ares_extensions.h)"""
+    _fields_ = [("lhs", InputVector), ("rhs", InputVector), ("arity", C.c_int), ("functor", C.c_int),
+                ("outType", C.c_int)]
+
+
+class FusedSelect(C.Structure):
+    """AresFusedSelect (include/ares_extensions.h): the query of AresFusedFilterSelect"""
+    _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("numDims", C.c_int),
+                ("dims", FusedExpr * 8)]
+
+
 # sizes pinned by include/ares_algorithm.h's static assertions (SURVEY.md 8b)
 ABI_SIZES = {CGoCallResHandle: 16, RecordID: 8, CuckooHashIndex: 40, DefaultValue: 24,
              VectorPartySlice: 56, ScratchSpaceVector: 16, ConstantVector: 24,
@@ -274,6 +286,24 @@ class Backend:
 
     def flags(self):
         return self._mem.GetFlags()
+
+    @property
+    def has_fused_select(self):
+        return hasattr(self._algo, "AresFusedFilterSelect")
+
+    def fused_filter_select(self, query, batch_rows, limit, out_keys, stream=None, device=0):
+        """AresFusedFilterSelect: rows written (AresError, "not fusable: ..." among them, as every call)."""
+        fn = self._algo.AresFusedFilterSelect  # AttributeError: this library has no such entry point
+        fn.argtypes = [C.POINTER(FusedSelect), C.c_int, C.c_int, DimensionVector, _S, _I]
+        fn.restype = CGoCallResHandle
+        return _check(fn(C.byref(query), int(batch_rows), int(limit), out_keys, stream, device))
+
+    def select_stats(self):
+        """{batches, declined, tiles, rows} of AresFusedFilterSelect since the process started."""
+        c = (C.c_ulonglong * 4)()
+        self._algo.AresSelectStats.argtypes, self._algo.AresSelectStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresSelectStats(c)
+        return {"batches": int(c[0]), "declined": int(c[1]), "tiles": int(c[2]), "rows": int(c[3])}
 
     def profiler_enable(self, on=True):
         self._algo.AresProfilerEnable(1 if on else 0)

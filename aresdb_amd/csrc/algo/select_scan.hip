@@ -1,0 +1,511 @@
+// AresFusedFilterSelect (include/ares_extensions.h): the non-aggregation query's batch — SELECT cols WHERE ... LIMIT n,
+// query/aql_nonaggr_batchexecutor.go — as ONE limit-aware pass over the source columns.
+//
+// The per-node sequence it replaces (InitIndexVector, a filter call per comparison, a transform call per dimension) reads
+// every filter column over the whole batch, compacts the survivors into an index vector and writes every survivor's
+// dimension row, whatever the limit is.  Here 4096-row tiles are handed out by ticket in row order; a tile evaluates the
+// filter conjunction from the columns (16 bytes per lane, 16-bit validity windows), ranks its survivors, obtains its
+// exclusive prefix by the decoupled look-back of lookback.hpp and writes the survivors' rows at prefix + rank — only ranks
+// below the limit.  A workgroup whose tile ends at or beyond the limit takes no further ticket, and a ticket taken after
+// some tile has reached the limit is published as empty without reading a column: with every row surviving, one round of
+// the grid is scanned whatever the batch size.  Values and validity bytes come from the functions the transform kernels
+// use (eval_quad, compare_tile, cvt32), so the bytes written equal the per-node sequence's for the same rows.
+//
+// Stores go straight to the slots: the survivors of a wavefront's quads have consecutive ranks, so each store instruction
+// of a wavefront covers one contiguous byte range, and a quad that survives whole is stored as one 16 / 8 / 4 byte access.
+#include "select_scan.hpp"
+
+#include <algorithm>
+#include <atomic>
+#include <map>
+#include <mutex>
+
+#include "ares_extensions.h"
+#include "binding.hpp"
+#include "common.hpp"
+#include "device_model.hpp"
+#include "dim_layout.hpp"
+#include "lookback.hpp"
+
+namespace ares {
+
+namespace {
+
+constexpr int Q = kSelectQuads;
+
+struct __attribute__((packed, aligned(1))) SU16 { uint16_t v; };
+struct __attribute__((packed, aligned(1))) SU32 { uint32_t v; };
+struct __attribute__((packed, aligned(1))) SU32x2 { uint32_t v[2]; };
+struct __attribute__((packed, aligned(1))) SU64 { uint64_t v; };
+struct __attribute__((packed, aligned(1))) SU64x2 { uint64_t v[2]; };
+
+__device__ __forceinline__ uint32_t ld_word(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void st_word(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// first row of quad q of this lane in the tile that starts at row0 (the geometry of filter_rows_kernel)
+__device__ __forceinline__ int64_t quad_row(int64_t row0, int q) { return row0 + (static_cast<int64_t>(q) * kSelectBlock + threadIdx.x) * 4; }
+
+// Values (widened as the transform kernels widen them) and validity nibbles of the lane's quads of one column; rows are
+// positions.  Positions at or beyond n read nothing: value 0, and a validity bit that the caller masks.
+__device__ __forceinline__ void load_column_tile(const FastOperands &f, int64_t row0, int n, uint32_t (&vals)[Q][4], uint32_t (&okb)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    const int64_t i0 = quad_row(row0, q);
+    const bool full = i0 + 3 < n;
+    uint32_t raw[4] = {0u, 0u, 0u, 0u};
+    if (f.step == 2) {
+      const uint16_t *v16 = reinterpret_cast<const uint16_t *>(f.vals);
+      if (full) {
+        const SU32x2 v = *reinterpret_cast<const SU32x2 *>(v16 + i0);
+        raw[0] = v.v[0] & 0xFFFFu; raw[1] = v.v[0] >> 16; raw[2] = v.v[1] & 0xFFFFu; raw[3] = v.v[1] >> 16;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (i0 + j < n) raw[j] = v16[i0 + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) vals[q][j] = f.akind == K_I32 ? static_cast<uint32_t>(static_cast<int32_t>(static_cast<int16_t>(raw[j]))) : raw[j];
+    } else if (f.step == 1) {
+      const uint8_t *v8 = reinterpret_cast<const uint8_t *>(f.vals);
+      if (full) {
+        const uint32_t v = reinterpret_cast<const SU32 *>(v8 + i0)->v;
+        raw[0] = v & 0xFFu; raw[1] = (v >> 8) & 0xFFu; raw[2] = (v >> 16) & 0xFFu; raw[3] = v >> 24;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (i0 + j < n) raw[j] = v8[i0 + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) vals[q][j] = f.akind == K_I32 ? static_cast<uint32_t>(static_cast<int32_t>(static_cast<int8_t>(raw[j]))) : raw[j];
+    } else {
+      if (full) {
+        if (f.streaming) {  // a column the plan reads once
+          typedef uint32_t V4 __attribute__((ext_vector_type(4)));
+          typedef V4 V4a __attribute__((aligned(4)));
+          const V4 v = __builtin_nontemporal_load(reinterpret_cast<const V4a *>(f.vals + i0));
+          raw[0] = v.x; raw[1] = v.y; raw[2] = v.z; raw[3] = v.w;
+        } else {
+          const U32x4 v = *reinterpret_cast<const U32x4 *>(f.vals + i0);
+#pragma unroll
+          for (int j = 0; j < 4; j++) raw[j] = v.v[j];
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+          if (i0 + j < n) raw[j] = f.vals[i0 + j];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) vals[q][j] = raw[j];
+    }
+    // 16-bit window of the bitmap from the byte of the quad's first row (one byte past a mode-2 bitmap lies in the values)
+    uint32_t window = 0xFFFFu;
+    const uint32_t bit0 = static_cast<uint32_t>(i0) + f.bitOff;
+    if (f.nulls && i0 < n) window = reinterpret_cast<const PU16 *>(f.nulls + (bit0 >> 3))->v;
+    okb[q] = (window >> (bit0 & 7u)) & 0xFu;
+  }
+}
+
+struct ExprConst {
+  DVal y;
+  FastDivisor fd;
+};
+__device__ __forceinline__ ExprConst expr_const(const FastOperands &f) {  // as store_tile (transform_kernels.hpp) prepares them
+  ExprConst c;
+  c.y.bits = f.bbits;
+  c.y.ok = f.bok;
+  c.y = cvt32(c.y, f.bkind, f.I);
+  const uint32_t mag = (f.I == K_I32 && static_cast<int32_t>(c.y.bits) < 0) ? 0u - c.y.bits : c.y.bits;
+  c.fd = make_fast_divisor(mag);
+  return c;
+}
+
+// A dimension of a 4 / 2 / 1 byte slot: the tile's survivors, ranks [base[q] ..) per quad, local ranks below `room` only.
+__device__ __forceinline__ void store_narrow_dim(const SelectDimD &D, int64_t row0, int n, const uint32_t (&alive)[Q], const uint32_t (&base)[Q],
+                                                 uint32_t excl, uint32_t room) {
+  uint32_t vals[Q][4], okb[Q];
+  load_column_tile(D.f, row0, n, vals, okb);
+  const ExprConst c = expr_const(D.f);
+  const int w = D.width;
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    if (!alive[q]) continue;
+    uint32_t rb[4], out[4];
+    const uint32_t rok = eval_quad(D.f, vals[q], okb[q], c.y, c.fd, rb);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      DVal x;
+      x.bits = rb[j];
+      x.ok = 1;
+      out[j] = w == 4 ? cvt32(x, D.f.rk, D.outKind).bits : rb[j];  // (a narrow slot takes the value truncated, integer kinds only)
+    }
+    const size_t at = static_cast<size_t>(excl) + base[q];
+    if (alive[q] == 0xFu && base[q] + 4u <= room) {  // the quad survives whole: one access per vector
+      if (w == 4) {
+        U32x4 o;
+#pragma unroll
+        for (int j = 0; j < 4; j++) o.v[j] = out[j];
+        *reinterpret_cast<U32x4 *>(D.values + 4 * at) = o;
+      } else if (w == 2) {
+        SU32x2 o;
+        o.v[0] = (out[0] & 0xFFFFu) | (out[1] << 16);
+        o.v[1] = (out[2] & 0xFFFFu) | (out[3] << 16);
+        *reinterpret_cast<SU32x2 *>(D.values + 2 * at) = o;
+      } else {
+        reinterpret_cast<SU32 *>(D.values + at)->v = (out[0] & 0xFFu) | ((out[1] & 0xFFu) << 8) | ((out[2] & 0xFFu) << 16) | (out[3] << 24);
+      }
+      reinterpret_cast<SU32 *>(D.nulls + at)->v = (rok & 1u) | ((rok & 2u) << 7) | ((rok & 4u) << 14) | ((rok & 8u) << 21);
+      continue;
+    }
+    uint32_t r = base[q];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (!((alive[q] >> j) & 1u)) continue;
+      if (r < room) {
+        const size_t to = static_cast<size_t>(excl) + r;
+        if (w == 4) reinterpret_cast<SU32 *>(D.values + 4 * to)->v = out[j];
+        else if (w == 2) reinterpret_cast<SU16 *>(D.values + 2 * to)->v = static_cast<uint16_t>(out[j]);
+        else D.values[to] = static_cast<uint8_t>(out[j]);
+        D.nulls[to] = static_cast<uint8_t>((rok >> j) & 1u);
+      }
+      r++;
+    }
+  }
+}
+
+// A dimension of an 8 / 16 byte slot: the surviving rows' stored bytes and validity bits (a gather).
+__device__ __forceinline__ void store_wide_dim(const SelectDimD &D, int64_t row0, const uint32_t (&alive)[Q], const uint32_t (&base)[Q], uint32_t excl,
+                                               uint32_t room) {
+  const uint8_t *src = reinterpret_cast<const uint8_t *>(D.f.vals);
+  const int w = D.width;
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    if (!alive[q]) continue;
+    const int64_t i0 = quad_row(row0, q);
+    const uint32_t bit0 = static_cast<uint32_t>(i0) + D.f.bitOff;
+    uint32_t okb = 0xFu;
+    if (D.f.nulls) okb = (reinterpret_cast<const PU16 *>(D.f.nulls + (bit0 >> 3))->v >> (bit0 & 7u)) & 0xFu;  // (alive: i0 is inside the batch)
+    uint32_t r = base[q];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (!((alive[q] >> j) & 1u)) continue;
+      if (r < room) {
+        const size_t to = static_cast<size_t>(excl) + r;
+        const size_t from = static_cast<size_t>(i0 + j);
+        if (w == 16) *reinterpret_cast<SU64x2 *>(D.values + 16 * to) = *reinterpret_cast<const SU64x2 *>(src + 16 * from);
+        else *reinterpret_cast<SU64 *>(D.values + 8 * to) = *reinterpret_cast<const SU64 *>(src + 8 * from);
+        D.nulls[to] = static_cast<uint8_t>((okb >> j) & 1u);
+      }
+      r++;
+    }
+  }
+}
+
+// (three workgroups per compute unit: 168 VGPRs, no scratch; a bound of four would spill)
+__global__ __launch_bounds__(kSelectBlock, 3) void select_scan_kernel(SelectPlanD p) {
+  __shared__ uint64_t sWave[kSelectBlock / 64];
+  __shared__ uint32_t sTileExcl;
+  __shared__ int sTile;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = p.batchRows;
+  uint32_t scanned = 0;  // (thread 0's copy is the one reported)
+  for (;;) {
+    if (threadIdx.x == 0) {
+      int t = static_cast<int>(atomicAdd(&p.state->ticket, 1u));
+      // A completed tile has reached the limit: this one is published as empty — its successors' look-back passes over it —
+      // and the workgroup leaves.  (Never tile 0: nothing completes before tile 0 has published.)
+      if (t > 0 && t < p.numTiles && ld_word(&p.state->stop)) {
+        st_status(p.status + t, kFlagAggregate);
+        t = -1;
+      }
+      sTile = t;
+    }
+    __syncthreads();
+    const int tile = sTile;
+    if (tile < 0 || tile >= p.numTiles) break;
+    const int64_t row0 = static_cast<int64_t>(tile) * kSelectTile;
+    scanned++;
+
+    // ---- the filter conjunction over the tile's rows
+    uint32_t in[Q], alive[Q];
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      const int64_t i0 = quad_row(row0, q);
+      in[q] = 0xFu;
+      if (i0 + 3 >= n) {
+        in[q] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++) in[q] |= (i0 + j < n ? 1u : 0u) << j;
+      }
+      alive[q] = in[q];
+    }
+    for (int k = 0; k < p.numFilters; k++) {
+      const FastOperands &f = p.filters[k];
+      uint32_t vals[Q][4], okb[Q], kb[Q];
+      load_column_tile(f, row0, n, vals, okb);
+      DVal y;
+      y.bits = f.bbits;
+      y.ok = f.bok;
+      y = cvt32(y, f.bkind, f.I);
+      compare_tile<Q>(f, vals, okb, in, y, kb);  // result validity is ignored (functor.hpp:903-915)
+#pragma unroll
+      for (int q = 0; q < Q; q++) alive[q] &= kb[q];
+    }
+
+    // ---- ranks in row order: quad q of every lane precedes quad q + 1 of any lane — four counts scanned as one word
+    uint64_t mine = 0;
+#pragma unroll
+    for (int q = 0; q < Q; q++) mine |= static_cast<uint64_t>(__popc(alive[q])) << (16 * q);
+    uint64_t incl = mine;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const uint64_t t = __shfl_up(incl, off);
+      if (lane >= off) incl += t;
+    }
+    if (lane == 63) sWave[wave] = incl;
+    __syncthreads();
+    uint64_t before = incl - mine, tileSum = 0;
+#pragma unroll
+    for (int w = 0; w < kSelectBlock / 64; w++) {
+      if (w < wave) before += sWave[w];
+      tileSum += sWave[w];
+    }
+    uint32_t base[Q], tileCount = 0;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      base[q] = tileCount + static_cast<uint32_t>((before >> (16 * q)) & 0xFFFFu);
+      tileCount += static_cast<uint32_t>((tileSum >> (16 * q)) & 0xFFFFu);
+    }
+
+    // ---- the tile's exclusive prefix
+    if (wave == 0) {
+      if (lane == 0) st_status(p.status + tile, (tile == 0 ? kFlagInclusive : kFlagAggregate) | tileCount);
+      uint64_t excl = 0;
+      if (tile > 0) {
+        excl = lookback_wave(p.status, tile, lane, &p.state->error);
+        if (lane == 0) st_status(p.status + tile, kFlagInclusive | (excl + tileCount));
+      }
+      if (lane == 0) {
+        sTileExcl = static_cast<uint32_t>(excl);
+        if (tile == p.numTiles - 1) st_word(&p.state->total, static_cast<uint32_t>(excl + tileCount));
+        if (excl + tileCount >= p.limit) st_word(&p.state->stop, 1u);
+      }
+    }
+    __syncthreads();
+    const uint32_t excl = sTileExcl;
+
+    // ---- the survivors' rows, ranks below the limit only
+    if (tileCount > 0 && excl < p.limit) {
+      const uint32_t room = p.limit - excl;
+      for (int d = 0; d < p.numDims; d++) {
+        const SelectDimD &D = p.dims[d];
+        if (D.width <= 4) store_narrow_dim(D, row0, n, alive, base, excl, room);
+        else store_wide_dim(D, row0, alive, base, excl, room);
+      }
+    }
+    if (static_cast<uint64_t>(excl) + tileCount >= p.limit) break;  // nothing more is wanted
+  }
+
+  // ---- the last workgroup to leave publishes the result in the caller's pinned words
+  if (threadIdx.x == 0) {
+    if (scanned) atomicAdd(&p.state->scanned, scanned);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    const uint32_t left = atomicAdd(&p.state->done, 1u);
+    if (left == gridDim.x - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      p.result[0] = ld_word(&p.state->stop) ? p.limit : ld_word(&p.state->total);
+      p.result[1] = ld_word(&p.state->error);
+      p.result[2] = ld_word(&p.state->scanned);
+    }
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+struct NotFusable : std::runtime_error {
+  explicit NotFusable(const std::string &why) : std::runtime_error("not fusable: " + why) {}
+};
+
+std::atomic<unsigned long long> g_stats[4];  // batches run, batches declined, tiles scanned, rows written
+
+bool select_enabled() {
+  static EnvSwitch<bool> on("ARES_SELECT", [](const char *e) { return !(e && e[0] == '0'); });
+  return on.get();
+}
+
+// workgroups of one launch: as many as the device holds at once; ARES_SELECT_GRID=n (tests) overrides
+int select_grid(int device) {
+  static EnvSwitch<int> forced("ARES_SELECT_GRID", [](const char *e) { return e ? atoi(e) : 0; });
+  const int f = forced.get();
+  if (f > 0) return std::min(f, kSelectGridCap);
+  static std::mutex mu;
+  static std::map<int, int> known;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find(device);
+  if (it != known.end()) return it->second;
+  int perCU = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, reinterpret_cast<const void *>(&select_scan_kernel), kSelectBlock, 0) != hipSuccess || perCU < 1) {
+    (void)hipGetLastError();
+    perCU = 4;
+  }
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) {
+    (void)hipGetLastError();
+    cus = 256;
+  }
+  return known[device] = std::max(1, std::min(perCU * cus, kSelectGridCap));
+}
+
+bool wide_type(int t) { return t == Int64 || t == Uint64 || t == GeoPoint || t == UUID; }
+
+void check_column(const AresFusedExpr &e, int batchRows) {
+  if (e.arity != 1 && e.arity != 2) throw NotFusable("arity");
+  if (e.lhs.Type != VectorPartyInput || (e.arity == 2 && e.rhs.Type != ConstantInput))
+    throw NotFusable("operands must be a main-table column and a constant");
+  if (static_cast<int64_t>(e.lhs.Vector.VP.Length) < batchRows) throw NotFusable("column shorter than the batch");
+}
+
+// a filter, or a dimension of a 4 / 2 / 1 byte slot: the operand shape of the fast transform / filter kernels
+FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream) {
+  check_column(e, batchRows);
+  if (wide_type(e.lhs.Vector.VP.DataType)) throw NotFusable("expression over a wide column");
+  InputVector ins[2] = {e.lhs, e.arity == 2 ? e.rhs : e.lhs};
+  EvalParams p;
+  CallTemps temps;
+  try {
+    build_params(ins, e.arity, stream, nullptr, nullptr, 0, e.functor, p, temps);
+  } catch (const std::invalid_argument &bad) {
+    throw NotFusable(bad.what());
+  }
+  FastOperands f;
+  if (!fast_operands(p, f, compareOnly)) throw NotFusable("expression shape");
+  f.idx = nullptr;
+  f.pad = 0;
+  return f;
+}
+
+// a bare Int64 / GeoPoint / UUID column into a slot of its own type
+FastOperands wide_operands(const AresFusedExpr &e, int batchRows, hipStream_t stream) {
+  check_column(e, batchRows);
+  const int t = e.lhs.Vector.VP.DataType;
+  if (e.arity != 1 || e.functor != Noop) throw NotFusable("expression over a wide column");
+  if (t != static_cast<int>(e.outType) || t == Uint64) throw NotFusable("a wide column goes into a slot of its own type");
+  OperandD op;
+  CallTemps temps;
+  try {
+    bind_operand(e.lhs, true, stream, op, temps);
+  } catch (const std::invalid_argument &bad) {
+    throw NotFusable(bad.what());
+  }
+  if (op.type != OP_COLUMN || op.mode > 2) throw NotFusable("column mode");
+  FastOperands f;
+  memset(&f, 0, sizeof(f));
+  f.vals = reinterpret_cast<const uint32_t *>(op.base + op.valuesOff);
+  f.nulls = op.mode == 2 ? op.base + op.nullsOff : nullptr;
+  f.bitOff = op.bitOff;
+  f.akind = op.kind;
+  f.arity = 1;
+  f.functor = Noop;
+  f.step = op.step;
+  return f;
+}
+
+int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int limit, const DimensionVector &outKeys, hipStream_t stream) {
+  if (!select_enabled()) throw NotFusable("switched off (ARES_SELECT=0)");
+  if (q.numFilters < 0 || q.numFilters > kSelectFilters) throw NotFusable("at most 4 filters");
+  if (q.numDims < 1 || q.numDims > kSelectDims) throw NotFusable("1..8 dimensions");
+  if (batchRows < 0) throw NotFusable("size");
+  DimLayoutD L;
+  try {
+    L = make_dim_layout(outKeys.NumDimsPerDimWidth);
+  } catch (const std::invalid_argument &) {
+    throw NotFusable("dimension vector layout");
+  }
+  if (L.numDims != q.numDims) throw NotFusable("dimension vector layout");
+
+  SelectPlanD plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.numFilters = q.numFilters;
+  plan.numDims = q.numDims;
+  for (int k = 0; k < q.numFilters; k++) plan.filters[k] = narrow_operands(q.filters[k], true, batchRows, stream);
+  const size_t capacity = static_cast<size_t>(outKeys.VectorCapacity > 0 ? outKeys.VectorCapacity : 0);
+  for (int d = 0; d < q.numDims; d++) {
+    const int t = q.dims[d].outType;
+    const bool narrow = t == Int8 || t == Uint8 || t == Int16 || t == Uint16 || t == Int32 || t == Uint32 || t == Float32;
+    if (!narrow && !(t == Int64 || t == GeoPoint || t == UUID)) throw NotFusable("dimension type");
+    SelectDimD &D = plan.dims[d];
+    D.width = step_in_bytes(t);
+    if (D.width != L.width[d]) throw NotFusable("dimension vector layout");
+    if (narrow) {
+      D.f = narrow_operands(q.dims[d], false, batchRows, stream);
+      if (D.width < 4 && !(D.f.rk == K_I32 || D.f.rk == K_U32)) throw NotFusable("float result into a narrow slot");
+      D.outKind = t == Int32 ? K_I32 : t == Uint32 ? K_U32 : K_F32;
+    } else {
+      D.f = wide_operands(q.dims[d], batchRows, stream);
+    }
+    D.values = outKeys.DimValues + static_cast<size_t>(L.valueOff[d]) * capacity;
+    D.nulls = outKeys.DimValues + static_cast<size_t>(L.valueBytes) * capacity + static_cast<size_t>(d) * capacity;
+  }
+  const int64_t wanted = limit < 0 ? batchRows : std::min<int64_t>(batchRows, limit);
+  if (static_cast<int64_t>(capacity) < wanted) throw std::invalid_argument("outKeys.VectorCapacity < min(batchRows, limit)");
+  if (wanted > 0 && !outKeys.DimValues) throw std::invalid_argument("null dimension vector");
+  if (wanted == 0) return 0;
+
+  // a 4-byte column that the plan reads once is loaded non-temporally
+  auto uses = [&](const uint32_t *vals) {
+    int c = 0;
+    for (int k = 0; k < plan.numFilters; k++) c += plan.filters[k].vals == vals;
+    for (int d = 0; d < plan.numDims; d++) c += plan.dims[d].f.vals == vals;
+    return c;
+  };
+  for (int k = 0; k < plan.numFilters; k++) plan.filters[k].streaming = uses(plan.filters[k].vals) == 1;
+  for (int d = 0; d < plan.numDims; d++) plan.dims[d].f.streaming = uses(plan.dims[d].f.vals) == 1;
+
+  flush_deferred_for_vector(device, outKeys, nullptr, 0);
+  grouped_note_write(device, outKeys);
+
+  plan.batchRows = batchRows;
+  plan.numTiles = static_cast<int>((static_cast<int64_t>(batchRows) + kSelectTile - 1) / kSelectTile);
+  plan.limit = limit < 0 ? 0xFFFFFFFFu : static_cast<uint32_t>(limit);
+  const size_t stateBytes = sizeof(SelectStateD) + sizeof(uint64_t) * static_cast<size_t>(plan.numTiles);
+  StreamBuffer ws((stateBytes + 15) / 16 * 16, stream);
+  hip_check(hipMemsetAsync(ws.get(), 0, (stateBytes + 15) / 16 * 16, stream), "hipMemsetAsync");
+  plan.state = ws.as<SelectStateD>();
+  plan.status = reinterpret_cast<uint64_t *>(ws.as<uint8_t>() + sizeof(SelectStateD));
+  volatile uint32_t *result = reinterpret_cast<volatile uint32_t *>(pinned_words());
+  plan.result = const_cast<uint32_t *>(result);
+  result[0] = 0u;
+  result[1] = 2u;  // (overwritten by the launch's last workgroup)
+  result[2] = 0u;
+  const int grid = std::min(select_grid(device), plan.numTiles);
+  ARES_LAUNCH("select_scan_kernel", select_scan_kernel, grid, kSelectBlock, stream, plan);
+  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+  ws.mark_idle();
+  if (result[1] == 2u) throw AlgorithmError("ERROR: select scan: the launch finished without publishing its result");
+  if (result[1] != 0u) throw AlgorithmError("ERROR: select scan: a look-back wait gave up");
+  const uint32_t rows = result[0];
+  g_stats[0]++;
+  g_stats[2] += result[2];
+  g_stats[3] += rows;
+  mem_note_dim_rows(device, outKeys, 0, rows);
+  return static_cast<int>(rows);
+}
+
+}  // namespace
+
+}  // namespace ares
+
+extern "C" CGoCallResHandle AresFusedFilterSelect(const AresFusedSelect *query, int batchRows, int limit, DimensionVector outKeys,
+                                                  void *cudaStream, int device) {
+  ARES_ABI_BEGIN(device)
+  if (!query) throw std::invalid_argument("null query");
+  try {
+    resHandle.res = ares::int_result(ares::fused_filter_select(device, *query, batchRows, limit, outKeys, reinterpret_cast<hipStream_t>(cudaStream)));
+  } catch (const ares::NotFusable &) {
+    ares::g_stats[1]++;
+    throw;
+  }
+  ARES_ABI_END("AresFusedFilterSelect")
+}
+
+extern "C" void AresSelectStats(unsigned long long *counters) {
+  if (!counters) return;
+  for (int i = 0; i < 4; i++) counters[i] = ares::g_stats[i].load();
+}

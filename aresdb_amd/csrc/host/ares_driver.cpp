@@ -58,6 +58,8 @@ struct AbiLibrary {
   decltype(&::Reduce) Reduce;
   decltype(&::HashReduce) HashReduce;
   decltype(&::AresFusedFilterHashReduce) FusedFilterHashReduce = nullptr;  // optional extension
+  decltype(&::AresFusedFilterSelect) FusedFilterSelect = nullptr;          // optional extension
+  decltype(&::Expand) Expand;
   // libmem
   decltype(&::DeviceAllocate) DeviceAllocate;
   decltype(&::DeviceFree) DeviceFree;
@@ -68,6 +70,8 @@ struct AbiLibrary {
   decltype(&::AsyncCopyDeviceToDevice) AsyncCopyDeviceToDevice;
   decltype(&::AsyncCopyDeviceToHost) AsyncCopyDeviceToHost;
   decltype(&::AsyncCopyHostToDevice) AsyncCopyHostToDevice;
+  decltype(&::HostAlloc) HostAlloc;
+  decltype(&::HostFree) HostFree;
   // optional (include/ares_extensions.h): libmem.so clears a freed block only where something wrote, so
   // whatever writes DeviceAllocate memory behind its back — a collective receiving into it — says so
   void (*NoteWrite)(int, const void *, size_t) = nullptr;
@@ -102,13 +106,17 @@ struct AbiLibrary {
     bind(algoHandle, "HyperLogLog", HyperLogLog);
     bind(algoHandle, "GeoBatchIntersects", GeoBatchIntersects);
     bind(algoHandle, "WriteGeoShapeDim", WriteGeoShapeDim);
+    bind(algoHandle, "Expand", Expand);
     FusedFilterHashReduce = reinterpret_cast<decltype(FusedFilterHashReduce)>(dlsym(algoHandle, "AresFusedFilterHashReduce"));
+    FusedFilterSelect = reinterpret_cast<decltype(FusedFilterSelect)>(dlsym(algoHandle, "AresFusedFilterSelect"));
     bind(memHandle, "DeviceAllocate", DeviceAllocate);
     bind(memHandle, "DeviceFree", DeviceFree);
     bind(memHandle, "WaitForCudaStream", WaitForCudaStream);
     bind(memHandle, "AsyncCopyDeviceToDevice", AsyncCopyDeviceToDevice);
     bind(memHandle, "AsyncCopyDeviceToHost", AsyncCopyDeviceToHost);
     bind(memHandle, "AsyncCopyHostToDevice", AsyncCopyHostToDevice);
+    bind(memHandle, "HostAlloc", HostAlloc);
+    bind(memHandle, "HostFree", HostFree);
     NoteWrite = reinterpret_cast<decltype(NoteWrite)>(dlsym(memHandle, "AresMemNoteWrite"));
     NoteActivity = reinterpret_cast<decltype(NoteActivity)>(dlsym(memHandle, "AresMemNoteActivity"));
   }
@@ -166,6 +174,9 @@ struct Plan {
   int measureNode, aggFunc, measureType;
   bool useHashReduction;
   bool useFusedExtension;
+  // a non-aggregation query (SELECT cols WHERE ... LIMIT n: the measure is a number literal, query/aql_compiler.go:1147-1153)
+  bool isNonAggregation;
+  int limit;  // < 0: none
   struct Foreign {
     AresForeignTable t;
     std::vector<VectorPartySlice> slices;
@@ -180,7 +191,8 @@ struct Plan {
         foreignFilters(p.foreignFilters, p.foreignFilters + p.numForeignFilters),
         dimNodes(p.dimNodes, p.dimNodes + p.numDims), dimTypes(p.dimTypes, p.dimTypes + p.numDims),
         measureNode(p.measureNode), aggFunc(p.aggFunc), measureType(p.measureType),
-        useHashReduction(p.useHashReduction != 0), useFusedExtension(p.useFusedExtension != 0) {
+        useHashReduction(p.useHashReduction != 0), useFusedExtension(p.useFusedExtension != 0),
+        isNonAggregation(p.isNonAggregation != 0), limit(p.limit) {
     for (int i = 0; i < p.numForeignTables; i++) {
       Foreign f;
       f.t = p.foreignTables[i];
@@ -240,6 +252,12 @@ struct AresQuery {
   std::vector<RecordID *> foreignRids;
   long calls = 0, fusedBatches = 0;
   bool fusedDeclined = false;  // the library rejected the plan once: stop asking
+  // non-aggregation queries (query/aql_nonaggr_batchexecutor.go): rows flushed to the host batch by batch
+  int maxBatchSize = 0;   // qc.maxBatchSizeAfterPrefilter (AresQuerySetMaxBatchSize); 0: the first batch's size
+  int batchRows = 0;      // rows of the current batch BEFORE its filters (batch.Size): what the dimension buffers are sized by
+  int rowsWritten = 0;    // qc.numberOfRowsWritten
+  bool done = false;      // OOPK.done: nothing more is wanted
+  std::vector<std::vector<uint8_t>> hostValues, hostNulls;  // the query's result on the host, per dimension in vector order
 
   AresQuery(AbiLibrary *l, const AresQueryPlan &p, int dev, void *s) : lib(l), plan(p), device(dev), stream(s) {
     // query/aql_compiler.go:1341-1362: dimensions ordered by width 16..1, then query order
@@ -276,6 +294,7 @@ struct AresQuery {
     columns = cols;
     numColumns = ncols;
     size = n;
+    batchRows = n;
     baseCounts = bc;
     startRow = start;
     indexVec = alloc<uint32_t>(static_cast<size_t>(n) * 4);
@@ -651,6 +670,112 @@ struct AresQuery {
     wait();
   }
   void postExec() { swapResultBuffers(); }
+
+  // ---- NonAggrBatchExecutorImpl (query/aql_nonaggr_batchexecutor.go) ----------------------------
+  std::vector<int> vectorWidths() const {
+    std::vector<int> widths;
+    for (int k = 0; k < NUM_DIM_WIDTH; k++)
+      for (int j = 0; j < ndw[k]; j++) widths.push_back(kDimWidths[k]);
+    return widths;
+  }
+  // getNumberOfRecordsNeeded (:107-117)
+  int recordsNeeded() const { return plan.limit < 0 ? -1 : std::max(plan.limit - rowsWritten, 0); }
+  // prepareForDimEval (:45-56): the two dimension buffers are allocated once, for the largest batch plus an eighth — and
+  // again when a batch arrives that is larger than what the query was told (nothing is carried over: every batch's rows
+  // have gone to the host)
+  void prepareForDimEval() {
+    // (the batch's rows before the filters, not the survivors: Expand may repeat the survivors up to the batch's size and
+    // beyond, and cuts its output at the capacity)
+    const int rows = std::max(maxBatchSize, batchRows);
+    if (dimVec[0] && rows + rows / 8 <= resultCapacity) return;
+    maxBatchSize = rows;
+    release(dimVec[0]); release(dimVec[1]);
+    resultCapacity = rows + rows / 8;
+    const size_t unit = std::max(plan.dimRowBytes(), 1);
+    dimVec[0] = alloc(static_cast<size_t>(resultCapacity) * unit);
+    dimVec[1] = alloc(static_cast<size_t>(resultCapacity) * unit);
+  }
+  // evalDimensions(0): the dimensions are written from row 0, the measure is not evaluated
+  void evalDimensions() {
+    for (size_t i = 0; i < plan.dimNodes.size(); i++) {
+      Action a;
+      a.kind = Action::DIMENSION;
+      a.dimType = plan.dimTypes[i];
+      a.prevResultSize = 0;
+      dimension_start_offsets(ndw, dimVectorIndex[i], resultCapacity, &a.valueOff, &a.nullOff);
+      if (plan.hasGeo && plan.geo.dimIndex == static_cast<int>(i)) {
+        if (size > 0 && plan.geo.shapeLatLongs) {
+          DimensionOutputVector dv;
+          dv.DimValues = dimVec[0] + a.valueOff;
+          dv.DimNulls = dimVec[0] + a.nullOff;
+          dv.DataType = Uint8;
+          calls++;
+          check(lib->WriteGeoShapeDim((plan.geo.numShapes + 31) / 32, dv, sizeBeforeGeoFilter, geoPredicateVec, stream, device));
+        }
+        continue;
+      }
+      processExpression(plan.dimNodes[i], a);
+    }
+  }
+  // expandDimensions (:58-74, time_series_aggregate.go:718-729)
+  void expandDimensions() {
+    const int wanted = recordsNeeded();
+    if (size != 0 && baseCounts) {
+      calls++;
+      resultSize = static_cast<int>(check(lib->Expand(dimensionVector(0), dimensionVector(1), baseCounts, indexVec, size, 0, stream, device)));
+      std::swap(dimVec[0], dimVec[1]);
+    } else {
+      resultSize = size;
+    }
+    if (wanted >= 0 && resultSize > wanted) resultSize = wanted;
+  }
+  void projectNonAggr() {
+    prepareForDimEval();
+    evalDimensions();
+    expandDimensions();
+    wait();
+    cleanupBeforeAggregation();
+  }
+  // postExec (:76-100): the batch's rows go to the host — HostAlloc, the per-dimension strided copies of
+  // asyncCopyDimensionVector, a wait — and are appended to the query's result (flushResultBuffer)
+  void postExecNonAggr() {
+    const std::vector<int> widths = vectorWidths();
+    if (hostValues.empty()) {
+      hostValues.resize(widths.size());
+      hostNulls.resize(widths.size());
+    }
+    const size_t n = static_cast<size_t>(resultSize);
+    if (n) {
+      uint8_t *host = reinterpret_cast<uint8_t *>(check(lib->HostAlloc(n * static_cast<size_t>(plan.dimRowBytes()))));
+      uint8_t *to = host;
+      for (size_t d = 0; d < widths.size(); d++) {
+        int64_t vo, no;
+        dimension_start_offsets(ndw, static_cast<int>(d), resultCapacity, &vo, &no);
+        check(lib->AsyncCopyDeviceToHost(to, dimVec[0] + vo, n * widths[d], stream, device));
+        to += n * widths[d];
+      }
+      for (size_t d = 0; d < widths.size(); d++) {
+        int64_t vo, no;
+        dimension_start_offsets(ndw, static_cast<int>(d), resultCapacity, &vo, &no);
+        check(lib->AsyncCopyDeviceToHost(to, dimVec[0] + no, n, stream, device));
+        to += n;
+      }
+      wait();
+      const uint8_t *from = host;
+      for (size_t d = 0; d < widths.size(); d++) {
+        hostValues[d].insert(hostValues[d].end(), from, from + n * widths[d]);
+        from += n * widths[d];
+      }
+      for (size_t d = 0; d < widths.size(); d++) {
+        hostNulls[d].insert(hostNulls[d].end(), from, from + n);
+        from += n;
+      }
+      check(lib->HostFree(host));
+    }
+    rowsWritten += resultSize;
+    if (recordsNeeded() == 0) done = true;
+    size = 0;
+  }
   void swapStreams() {
     if (otherStream) std::swap(stream, otherStream);
   }
@@ -720,7 +845,64 @@ struct AresQuery {
     return true;
   }
 
+  // The non-aggregation batch through AresFusedFilterSelect (include/ares_extensions.h): filters and dimensions of a batch
+  // without base counts, joins or geo in one limit-aware call.  false: this batch takes the ordinary sequence.
+  bool runBatchFusedSelect(const VectorPartySlice *cols, int ncols, int n) {
+    if (!plan.useFusedExtension || fusedDeclined || !lib->FusedFilterSelect) return false;
+    if (baseCounts || plan.hasGeo || !plan.foreign.empty() || !plan.foreignFilters.empty()) return false;
+    if (plan.dimNodes.empty() || plan.dimNodes.size() > 8 || plan.filters.size() > 4) return false;
+    columns = cols;
+    numColumns = ncols;
+    Pod<AresFusedSelect> q;
+    q->numFilters = static_cast<int>(plan.filters.size());
+    for (size_t i = 0; i < plan.filters.size(); i++)
+      if (!fusedExpr(plan.filters[i], Bool, &q->filters[i])) return false;
+    q->numDims = static_cast<int>(plan.dimNodes.size());
+    for (size_t i = 0; i < plan.dimNodes.size(); i++)
+      if (!fusedExpr(plan.dimNodes[i], plan.dimTypes[i], &q->dims[dimVectorIndex[i]])) return false;
+    size = n;
+    batchRows = n;
+    prepareForDimEval();
+    calls++;
+    CGoCallResHandle h = lib->FusedFilterSelect(&q.get(), n, recordsNeeded(), dimensionVector(0), stream, device);
+    if (h.pStrErr && strncmp(h.pStrErr, "not fusable", 11) == 0) {
+      free(const_cast<char *>(h.pStrErr));
+      fusedDeclined = true;  // (as runBatchFused: the plan's shape does not change, stop asking)
+      size = 0;
+      return false;
+    }
+    resultSize = static_cast<int>(check(h));
+    wait();
+    for (void *p : ownedColumns) release(p);  // the batch's input columns (query/aql_processor.go:695-699)
+    ownedColumns.clear();
+    postExecNonAggr();
+    fusedBatches++;
+    return true;
+  }
+
+  void runBatchNonAggr(const VectorPartySlice *cols, int ncols, int n, uint32_t *bc, uint32_t start) {
+    if (done) {  // query/aql_processor.go:119, :185, :227: no batch runs once nothing more is wanted
+      ownedColumns.clear();  // (its columns stay the caller's)
+      return;
+    }
+    baseCounts = bc;
+    if (!runBatchFusedSelect(cols, ncols, n)) {
+      prepareForFiltering(cols, ncols, n, bc, start);
+      preExec();
+      filter();
+      join();
+      projectNonAggr();
+      // reduce(): nothing to do
+      postExecNonAggr();
+    }
+    swapStreams();
+  }
+
   void runBatch(const VectorPartySlice *cols, int ncols, int n, uint32_t *bc, uint32_t start) {
+    if (plan.isNonAggregation) {
+      runBatchNonAggr(cols, ncols, n, bc, start);
+      return;
+    }
     baseCounts = bc;
     if (runBatchFused(cols, ncols, n)) {
       swapStreams();
@@ -800,7 +982,9 @@ int AresQueryRunResidentBatches(AresQuery *q, const VectorPartySlice *columns, i
   return 0;
 }
 
-int AresQueryResultSize(const AresQuery *q) { return q->resultSize; }
+int AresQueryResultSize(const AresQuery *q) { return q->plan.isNonAggregation ? q->rowsWritten : q->resultSize; }
+int AresQueryDone(const AresQuery *q) { return q->done ? 1 : 0; }
+void AresQuerySetMaxBatchSize(AresQuery *q, int rows) { q->maxBatchSize = rows > 0 ? rows : 0; }
 int AresQueryResultCapacity(const AresQuery *q) { return q->resultCapacity; }
 uint8_t *AresQueryDimensionVector(const AresQuery *q) { return q->dimVec[0]; }
 uint8_t *AresQueryMeasureVector(const AresQuery *q) { return q->measureVec[0]; }
@@ -830,6 +1014,12 @@ int AresQueryFetchHLL(AresQuery *q, uint16_t *regCounts, uint8_t *hllVector, cha
 
 int AresQueryFetch(AresQuery *q, uint8_t *dims, uint8_t *measures, char *err, int errLen) {
   try {
+    if (q->plan.isNonAggregation) {  // the rows are on the host already: dimension values in vector order, then validity bytes
+      uint8_t *out = dims;
+      for (const std::vector<uint8_t> &v : q->hostValues) out = std::copy(v.begin(), v.end(), out);
+      for (const std::vector<uint8_t> &v : q->hostNulls) out = std::copy(v.begin(), v.end(), out);
+      return 0;
+    }
     const int n = q->resultSize;
     std::vector<int> widths;
     for (int k = 0; k < NUM_DIM_WIDTH; k++)

@@ -71,6 +71,14 @@ typedef struct {
    * any other plan, and any batch the library declines, runs the ordinary sequence */
   int useFusedExtension;
   const AresGeoIntersection *geo; /* NULL: no geo intersection in this query */
+  /* A non-aggregation query (SELECT cols WHERE ... LIMIT n; the AQL compiler flags one when the measure is a number
+   * literal, query/aql_compiler.go:1147-1153) runs as query/aql_nonaggr_batchexecutor.go does: filters and joins, the
+   * dimensions written from row 0, Expand when the batch has base counts, the rows cut to what is still wanted, no
+   * measure and no reduction, the batch's rows copied to the host, and the query is DONE once `limit` rows exist
+   * (limit < 0: none).  With useFusedExtension a batch without base counts, joins or geo is tried through
+   * AresFusedFilterSelect first; once the library has declined the plan ("not fusable") the query stops asking.  Both 0: an aggregation query, as before. */
+  int isNonAggregation;
+  int limit;
 } AresQueryPlan;
 
 typedef struct AresQuery AresQuery; /* oopkBatchContext + executor of one query on one device */
@@ -89,7 +97,15 @@ int AresQueryRunBatch(AresQuery *q, const VectorPartySlice *columns, int numColu
  * counts, start row 0, isLastBatch = 0) without returning to the caller in between. */
 int AresQueryRunResidentBatches(AresQuery *q, const VectorPartySlice *columns, int numColumns, const int *sizes, int numBatches,
                                 char *err, int errLen);
-int AresQueryResultSize(const AresQuery *q);
+int AresQueryResultSize(const AresQuery *q); /* a non-aggregation query: the rows written so far, over all batches */
+/* Non-aggregation queries: 1 once nothing more is wanted — a batch run on a done query issues no ABI call
+ * (query/aql_processor.go:119, :185, :227), and columns adopted for it (AresQueryAdoptColumns) stay the caller's. */
+int AresQueryDone(const AresQuery *q);
+/* Non-aggregation queries: the largest batch the query will see (the reference's maxBatchSizeAfterPrefilter); the two
+ * dimension buffers are allocated once, for that many rows plus an eighth.  Not called: the first batch's size (its rows
+ * before the filters, like every size here), and the
+ * buffers are allocated again should a larger batch arrive. */
+void AresQuerySetMaxBatchSize(AresQuery *q, int rows);
 int AresQueryResultCapacity(const AresQuery *q);
 uint8_t *AresQueryDimensionVector(const AresQuery *q); /* device pointer, capacity stride */
 uint8_t *AresQueryMeasureVector(const AresQuery *q);
@@ -98,6 +114,7 @@ long AresQueryNumFusedBatches(const AresQuery *q);     /* batches that took the 
 /* D2H of the result (query/aql_processor.go:641-671): dims = for each dim in vector order
  * resultSize*width value bytes, then numDims x resultSize validity bytes; measures. */
 int AresQueryFetch(AresQuery *q, uint8_t *dims, uint8_t *measures, char *err, int errLen);
+/* (a non-aggregation query: the rows accumulated on the host, in the same columnar form; measures is ignored) */
 /* HyperLogLog queries (aggFunc == AGGR_HLL, measure = GetHLLValue(column) into a Uint32 vector):
  * the executor must know which batch is the last one (query/aql_batchexecutor.go:62-100); after it,
  * the result is the dimension columns (AresQueryFetch, measures may be NULL), the registers per

@@ -41,7 +41,8 @@ class QueryPlanC(C.Structure):
                 ("measureNode", C.c_int), ("aggFunc", C.c_int), ("measureType", C.c_int),
                 ("useHashReduction", C.c_int),
                 ("foreignTables", C.POINTER(ForeignTableC)), ("numForeignTables", C.c_int),
-                ("useFusedExtension", C.c_int), ("geo", C.POINTER(GeoIntersectionC))]
+                ("useFusedExtension", C.c_int), ("geo", C.POINTER(GeoIntersectionC)),
+                ("isNonAggregation", C.c_int), ("limit", C.c_int)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -75,7 +76,8 @@ def _driver():
         lib.AresQueryRunResidentBatches.restype = C.c_int
         for name, res in (("AresQueryResultSize", C.c_int), ("AresQueryResultCapacity", C.c_int),
                           ("AresQueryDimensionVector", C.c_void_p), ("AresQueryMeasureVector", C.c_void_p),
-                          ("AresQueryNumCalls", C.c_long), ("AresQueryNumFusedBatches", C.c_long)):
+                          ("AresQueryNumCalls", C.c_long), ("AresQueryNumFusedBatches", C.c_long),
+                          ("AresQueryDone", C.c_int)):
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = [C.c_void_p], res
         lib.AresQueryFetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
@@ -83,6 +85,7 @@ def _driver():
         lib.AresQueryDestroy.argtypes = [C.c_void_p]
         lib.AresQuerySetLastBatch.argtypes = [C.c_void_p, C.c_int]
         lib.AresQuerySetSecondStream.argtypes = [C.c_void_p, C.c_void_p]
+        lib.AresQuerySetMaxBatchSize.argtypes, lib.AresQuerySetMaxBatchSize.restype = [C.c_void_p, C.c_int], None
         lib.AresQueryAdoptColumns.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]
         lib.AresCommCreate.argtypes, lib.AresCommCreate.restype = [C.c_int, C.c_int, ALLGATHER_FN, C.c_void_p], C.c_void_p
         lib.AresCommRcclUniqueId.argtypes, lib.AresCommRcclUniqueId.restype = [C.c_void_p, C.c_char_p, C.c_int], C.c_int
@@ -189,6 +192,8 @@ class NativeQuery:
         pc.useHashReduction = int(plan.use_hash_reduction)
         pc.foreignTables, pc.numForeignTables = arr(ForeignTableC, fts), len(fts)
         pc.useFusedExtension = int(getattr(plan, "use_fused_extension", False))
+        pc.isNonAggregation = int(getattr(plan, "is_non_aggregation", False))
+        pc.limit = int(getattr(plan, "limit", -1))
         geo = getattr(plan, "geo", None)
         if geo is not None:
             g = GeoIntersectionC()
@@ -256,6 +261,15 @@ class NativeQuery:
     @property
     def fused_batches(self):
         return _driver().AresQueryNumFusedBatches(self._q)
+
+    @property
+    def done(self):
+        """a non-aggregation query: nothing more is wanted — further batches issue no ABI call"""
+        return bool(_driver().AresQueryDone(self._q))
+
+    def set_max_batch_size(self, rows):
+        """a non-aggregation query: the largest batch it will see (its dimension buffers are allocated once for it)"""
+        _driver().AresQuerySetMaxBatchSize(self._q, int(rows))
 
     # -- the attributes shard_merge.merge_shard_results reads from a batch context --------------------
     @property

@@ -95,6 +95,10 @@ class QueryPlan:
     foreign_tables: List[ForeignTable] = field(default_factory=list)
     foreign_filters: List[object] = field(default_factory=list)
     geo: Optional[GeoIntersection] = None
+    # A non-aggregation query (SELECT cols WHERE ... LIMIT n; the AQL compiler flags one when the measure is a number
+    # literal, query/aql_compiler.go:1147-1153): run as query/aql_nonaggr_batchexecutor.go does; limit < 0: none.
+    is_non_aggregation: bool = False
+    limit: int = -1
 
     @property
     def measure_bytes(self):
@@ -180,6 +184,14 @@ class BatchContext:
         self.hll_vector = 0
         self.hll_dim_reg_count = 0
         self.hll_vector_size = 0
+        # non-aggregation queries (query/aql_nonaggr_batchexecutor.go): rows flushed to the host batch by batch
+        self.max_batch_size = 0   # qc.maxBatchSizeAfterPrefilter; 0: the first batch's size
+        self.batch_rows = 0
+        self.rows_written = 0     # qc.numberOfRowsWritten
+        self.done = False         # OOPK.done: nothing more is wanted
+        widths = [w for w, c in zip(DIM_WIDTHS, self.ndw) for _ in range(c)]
+        self.host_values = [bytearray() for _ in widths]  # the query's result on the host, per dimension in vector order
+        self.host_nulls = [bytearray() for _ in widths]
 
     # -- allocation helpers (device_allocator.go semantics: every byte is tracked and freed) --------
     def _alloc(self, nbytes):
@@ -197,6 +209,7 @@ class BatchContext:
     def prepare_for_filtering(self, columns, size, base_counts=None, start_row=0):
         self.columns = columns
         self.size = size
+        self.batch_rows = size  # rows before the filters (batch.Size)
         self.start_row = start_row
         self.base_counts = base_counts
         self.index_vec = self._alloc(size * 4)
@@ -249,6 +262,26 @@ class BatchContext:
         mb = plan.measure_bytes
         realloc(self.measure_vec, mb, lambda to, frm: self.result_size and self.be.call(
             "AsyncCopyDeviceToDevice", to, frm, self.result_size * mb, self.stream, self.device))
+
+    # -- aql_nonaggr_batchexecutor.go:45-56 ---------------------------------------------------------
+    def records_needed(self):
+        """getNumberOfRecordsNeeded (:107-117)"""
+        return -1 if self.plan.limit < 0 else max(self.plan.limit - self.rows_written, 0)
+
+    def prepare_for_dim_eval(self):
+        """The two dimension buffers are allocated once, for the largest batch plus an eighth — and again when a batch
+        arrives that is larger than what the query was told (nothing is carried over: every batch's rows have gone to the
+        host)."""
+        rows = max(self.max_batch_size, self.batch_rows)  # the batch's rows before the filters, not the survivors
+        if self.dim_vec[0] and rows + rows // 8 <= self.result_capacity:
+            return
+        self.max_batch_size = rows
+        self._free(self.dim_vec[0])
+        self._free(self.dim_vec[1])
+        self.result_capacity = rows + rows // 8
+        unit = max(self.plan.dim_row_bytes, 1)
+        self.dim_vec[0] = self._alloc(self.result_capacity * unit)
+        self.dim_vec[1] = self._alloc(self.result_capacity * unit)
 
     # -- time_series_aggregate.go:745-769 ------------------------------------------------------------
     def allocate_stack_frame(self, data_type):
@@ -463,6 +496,19 @@ class BatchExecutor:
         """owned_columns: callables releasing the batch's device columns; the Go host frees them in
         cleanupBeforeAggregation, i.e. between project() and reduce()."""
         c = self.ctx
+        if c.plan.is_non_aggregation:
+            # NonAggrBatchExecutorImpl; no batch runs once nothing more is wanted (query/aql_processor.go:119, :185, :227)
+            if c.done:
+                return
+            c.owned_columns = list(owned_columns)
+            c.prepare_for_filtering(columns, size, base_counts, start_row)
+            self.pre_exec()
+            self.filter()
+            self.join()
+            self.project_non_aggr()
+            # reduce(): nothing to do
+            self.post_exec_non_aggr()
+            return
         c.owned_columns = list(owned_columns)
         self.is_last_batch = is_last_batch
         c.prepare_for_filtering(columns, size, base_counts, start_row)
@@ -472,6 +518,60 @@ class BatchExecutor:
         self.project()
         self.reduce()
         self.post_exec()
+
+    # -- NonAggrBatchExecutorImpl (query/aql_nonaggr_batchexecutor.go) ------------------------------------
+    def project_non_aggr(self):
+        c = self.ctx
+        c.prepare_for_dim_eval()
+        for i, dim in enumerate(c.plan.dimensions):  # evalDimensions(0): from row 0; the measure is not evaluated
+            vo, no = dimension_start_offsets(c.ndw, c.dim_index[i], c.result_capacity)
+            if c.plan.geo is not None and c.plan.geo.dim_index == i:
+                c.write_geo_shape_dim(vo, no, self.size_before_geo, 0)
+                continue
+            c.process_expression(dim.expr, c.make_dimension_action(dim, vo, no, 0))
+        # expandDimensions (:58-74, time_series_aggregate.go:718-729)
+        wanted = c.records_needed()
+        if c.size != 0 and c.base_counts:
+            c.result_size = c.call("Expand", c.dimension_vector(0), c.dimension_vector(1), c.base_counts, c.index_vec,
+                                   c.size, 0, c.stream, c.device)
+            c.dim_vec[0], c.dim_vec[1] = c.dim_vec[1], c.dim_vec[0]
+        else:
+            c.result_size = c.size
+        if wanted >= 0 and c.result_size > wanted:
+            c.result_size = wanted
+        c.be.wait(c.stream, c.device)
+        c.cleanup_before_aggregation()
+
+    def post_exec_non_aggr(self):
+        """postExec (:76-100): HostAlloc, the per-dimension strided copies of asyncCopyDimensionVector, a wait; the rows
+        are appended to the query's result (flushResultBuffer)."""
+        c = self.ctx
+        be, n = c.be, c.result_size
+        widths = [w for w, k in zip(DIM_WIDTHS, c.ndw) for _ in range(k)]
+        if n:
+            host = be.call("HostAlloc", n * c.plan.dim_row_bytes)
+            to = host
+            for d, w in enumerate(widths):
+                vo, _ = dimension_start_offsets(c.ndw, d, c.result_capacity)
+                be.d2h(to, c.dim_vec[0] + vo, n * w, c.stream, c.device)
+                to += n * w
+            for d in range(len(widths)):
+                _, no = dimension_start_offsets(c.ndw, d, c.result_capacity)
+                be.d2h(to, c.dim_vec[0] + no, n, c.stream, c.device)
+                to += n
+            be.wait(c.stream, c.device)
+            frm = host
+            for d, w in enumerate(widths):
+                c.host_values[d] += C.string_at(frm, n * w)
+                frm += n * w
+            for d in range(len(widths)):
+                c.host_nulls[d] += C.string_at(frm, n)
+                frm += n
+            be.call("HostFree", host)
+        c.rows_written += n
+        if c.records_needed() == 0:
+            c.done = True
+        c.size = 0
 
     def pre_exec(self):
         c = self.ctx
@@ -562,6 +662,14 @@ def fetch_results(ctx: BatchContext):
         be.d2h(meas.ctypes.data_as(C.c_void_p), ctx.measure_vec[0], meas.nbytes, ctx.stream, ctx.device)
     be.wait(ctx.stream, ctx.device)
     return dims, valids, meas
+
+
+def fetch_select_results(ctx: BatchContext):
+    """The rows a non-aggregation query has accumulated on the host, as fetch_results returns dimensions: per-dimension
+    value and validity arrays in query dimension order."""
+    dims = [np.frombuffer(bytes(ctx.host_values[ctx.dim_index[i]]), np.uint8) for i in range(len(ctx.plan.dimensions))]
+    valids = [np.frombuffer(bytes(ctx.host_nulls[ctx.dim_index[i]]), np.uint8) for i in range(len(ctx.plan.dimensions))]
+    return dims, valids
 
 
 def fetch_hll_results(ctx: BatchContext):

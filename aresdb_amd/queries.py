@@ -43,3 +43,12 @@ def c2_plan(threshold):
     return QueryPlan(filters=[Binary(abi.LessThan, Col("ts"), Const(threshold))], dimensions=[],
                      measure=Const(1), agg=abi.AGGR_SUM_UNSIGNED, measure_type=abi.Uint32,
                      use_hash_reduction=False)
+
+
+def select_plan(columns, filters, limit=-1, use_fused_extension=False):
+    """A non-aggregation query, SELECT columns WHERE filters LIMIT limit (limit < 0: none): `columns` = [(expression, output
+    DataType)], `filters` = comparison expressions.  The AQL compiler flags such a query by its measure, the number literal 1
+    (query/aql_compiler.go:1147-1153); the non-aggregation executor never evaluates it."""
+    return QueryPlan(filters=list(filters), dimensions=[DimensionSpec(e, t) for e, t in columns], measure=Const(1),
+                     agg=abi.AGGR_SUM_UNSIGNED, measure_type=abi.Uint32, use_hash_reduction=True,
+                     use_fused_extension=use_fused_extension, is_non_aggregation=True, limit=limit)

@@ -130,6 +130,21 @@ def compare_results(got, want, rel=1e-6):
         assert abs(g - v) <= rel * max(1.0, abs(v)), (k, g, v)
 
 
+def run_select_native(be, plan, batches):
+    """A non-aggregation query through the C++ driver: (rows, per-dimension value bytes, validity bytes, fused batches)."""
+    from .driver import NativeQuery
+    q = NativeQuery(be, plan, list(batches[0][0].keys()))
+    for cols, valid in batches:
+        dev = {k: DeviceColumn(be, t, v, valid=valid[k]) for k, (t, v) in cols.items()}
+        q.run({k: d.vp for k, d in dev.items()}, len(next(iter(cols.values()))[1]))
+        for d in dev.values():
+            d.free()
+    dims, valids, _ = q.fetch()
+    out = (q.result_size, [bytes(d) for d in dims], [bytes(v) for v in valids], q.fused_batches)
+    q.release()
+    return out
+
+
 def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
     rng = np.random.default_rng(seed)
     data = [synth_batch(rng, n, null_fraction=0.01) for _ in range(batches)]
@@ -137,3 +152,15 @@ def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
         got, _ = run_query(hip, c3_plan(use_hash), data)
         want, _ = run_query(oracle, c3_plan(use_hash), data)
         compare_results(got, want)
+    # one small select (SELECT floor(ts, 3600), d1, m WHERE d1 < 90 LIMIT n + 100): the fused select scan against the
+    # ordinary sequence on the product, and against the oracle
+    from .executor import Binary, Col, Const
+    from .queries import select_plan
+    columns = [(Binary(abi.Floor, Col("ts"), Const(3600)), abi.Uint32), (Col("d1"), abi.Uint32), (Col("m"), abi.Float32)]
+    filters = [Binary(abi.LessThan, Col("d1"), Const(90))]
+    plain = run_select_native(hip, select_plan(columns, filters, n + 100), data)
+    fused = run_select_native(hip, select_plan(columns, filters, n + 100, use_fused_extension=True), data)
+    want = run_select_native(oracle, select_plan(columns, filters, n + 100), data)
+    assert plain[0] == n + 100 and plain[3] == 0 and fused[3] == 2, (plain[0], plain[3], fused[3])
+    assert fused[:3] == plain[:3], "the fused select scan and the ordinary sequence disagree"
+    assert plain[:3] == want[:3], "the select query disagrees with the oracle"

@@ -93,6 +93,34 @@ def trips_plan(count=False, time_range=TIME_RANGE):
                      use_hash_reduction=True)
 
 
+def trips_select_plan(limit=-1, fused=False, time_range=TIME_RANGE):
+    """SELECT request_at, city_id, fare, key WHERE the two time filters AND status == completed LIMIT limit: the
+    non-aggregation query over the trips table plus a UUID `key` column (key_column), the typical shape of such a query."""
+    from .queries import select_plan
+    filters = [Binary(abi.GreaterThanOrEqual, Col("request_at"), Const(int(time_range[0]))),
+               Binary(abi.LessThan, Col("request_at"), Const(int(time_range[1]))),
+               Binary(abi.Equal, Col("status"), Const(COMPLETED))]
+    columns = [(Col("request_at"), abi.Uint32), (Col("city_id"), abi.Uint16), (Col("fare"), abi.Float32), (Col("key"), abi.UUID)]
+    return select_plan(columns, filters, limit, use_fused_extension=fused)
+
+
+def key_column(n, gen, device, null_fraction=0.01) -> ResidentColumn:
+    """a UUID column of random 16-byte keys for the select query: [validity bitmap][n x 16 value bytes]"""
+    raw = torch.randint(-(1 << 31), (1 << 31) - 1, (n * 4,), dtype=torch.int32, device=device, generator=gen).view(torch.uint8)
+    if null_fraction <= 0:
+        return ResidentColumn(raw, 0, abi.UUID, n, False)
+    valid = (torch.rand((n,), dtype=torch.float32, device=device, generator=gen) >= null_fraction).to(torch.uint8)
+    nb = (n + 7) // 8
+    if nb * 8 != n:
+        valid = torch.cat([valid, torch.zeros(nb * 8 - n, dtype=torch.uint8, device=device)])
+    weights = (1 << torch.arange(8, device=device, dtype=torch.int32)).to(torch.uint8)
+    off = _align64(nb)
+    blob = torch.zeros(off + raw.numel() + 64, dtype=torch.uint8, device=device)
+    blob[:nb] = (valid.view(nb, 8) * weights).sum(dim=1, dtype=torch.int32).to(torch.uint8)
+    blob[off:off + raw.numel()] = raw
+    return ResidentColumn(blob, off, abi.UUID, n, True)
+
+
 def _valid(rc):
     return rc.valid()
 

@@ -179,6 +179,37 @@ CGoCallResHandle AresFusedFilterHashReduce(const AresFusedQuery *query, int batc
                                            uint8_t *prevValues, int prevSize, DimensionVector outKeys,
                                            uint8_t *outValues, void *cudaStream, int device);
 
+/* Fused select scan: the batch of a NON-AGGREGATION query (SELECT cols WHERE ... LIMIT n, query/aql_nonaggr_batchexecutor.go)
+ * in one limit-aware pass over the source columns.  It replaces, for one batch, the call sequence
+ *   InitIndexVector, Unary/BinaryFilter x numFilters, Unary/BinaryTransform x numDims into rows [0, survivors) of outKeys
+ * with the rows cut at `limit` (< 0: none): the dimension rows (values, one validity byte per dimension) of the first
+ * min(survivors, limit) surviving rows, in ascending row order, are written into rows [0, res) of outKeys, byte for byte what
+ * the sequence stores for those rows (value bytes of null rows included); rows at or beyond res are not written;
+ * res = that count.  Tiles of 4096 rows are handed out in row order, and once a tile's inclusive survivor count has reached
+ * the limit no further tile reads a column: a small limit costs one round of the grid whatever the batch size.
+ *
+ * Shapes accepted (anything else returns an error string starting with "not fusable" before anything is launched, and the
+ * host simply runs the ordinary sequence): 0-4 filters, each a comparison of a main-table column (1-, 2- or 4-byte type,
+ * modes 1/2) with a constant; 1-8 dimensions in vector order (dims[d] is slot d of outKeys, widths descending), each either
+ * a main-table column of a 1-, 2- or 4-byte type, bare or combined with a constant by a binary functor, into a slot of
+ * 4 / 2 / 1 bytes (outType = the slot's DataType; a narrow slot takes integer results), or a BARE Int64 / GeoPoint / UUID
+ * column (modes 1/2) into a slot of its own type.  Declined: Bool and Uint64 columns, mode 0 / 3 columns, foreign-table and
+ * array operands, expressions over a wide column.  outKeys.VectorCapacity must be at least batchRows (limit < 0) or
+ * min(batchRows, limit); batchRows == 0 or limit == 0 returns 0 and launches nothing.
+ * Environment (both obey AresReloadEnv): ARES_SELECT=0 declines always; ARES_SELECT_GRID=n (tests) sets the number of
+ * workgroups, at most 2048. */
+typedef struct {
+  int numFilters;
+  AresFusedExpr filters[4];
+  int numDims;
+  AresFusedExpr dims[8]; /* outType = the slot's DataType */
+} AresFusedSelect;
+
+CGoCallResHandle AresFusedFilterSelect(const AresFusedSelect *query, int batchRows, int limit /* < 0: none */,
+                                       DimensionVector outKeys, void *cudaStream, int device);
+/* {batches run, batches declined, tiles scanned, rows written} since process start */
+void AresSelectStats(unsigned long long *counters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -256,6 +256,72 @@ def trips_leg(be, dev, rows, batch_rows=1 << 26, steps=3):
     return out
 
 
+def select_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1)):
+    """The non-aggregation query over the trips shard (aresdb_amd/trips.py: trips_select_plan — request_at, city_id, fare and a
+    UUID key WHERE the two time filters AND status == completed) with limits 100, 1 M and none, through the ordinary sequence
+    and through AresFusedFilterSelect, in the C++ driver.  The limited runs of the two paths are compared row for row, the
+    unlimited ones by their row counts and first million rows.  One JSON row per (limit, path): ms per step and per 1 B rows,
+    the per-kernel split, and for the unlimited query the algorithmic bytes — the five columns read once + dimRowBytes per
+    survivor written — against 8 TB/s."""
+    from aresdb_amd import trips
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(12)
+    batches = trips.trips_shard(rows, batch_rows, seed=11, device=dev)
+    for b in batches:
+        b["key"] = trips.key_column(b["fare"].length, gen, dev)
+    names = [n for n, _ in trips.COLUMNS] + ["key"]
+    vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    col_bytes = 4 + 2 + 1 + 4 + 16 + 5 / 8  # the five columns + their validity bits
+    row_bytes = 4 + 2 + 4 + 16 + 4           # dimRowBytes: the four slots + one validity byte each
+    out, first = [], {}
+    for limit in limits:
+        for fused in (False, True):
+            plan = trips.trips_select_plan(limit=limit, fused=fused)
+            packed = None
+            def run():
+                nonlocal packed
+                q = NativeQuery(be, plan, names, streams=streams)
+                q.set_max_batch_size(batch_rows)
+                if packed is None:
+                    packed = q.pack_batches(vps)
+                q.run_batches(packed)
+                return q
+            run().release()
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps):
+                q = run(); q.release()
+            torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+            be.profiler_enable(True)
+            stats0 = be.select_stats()
+            q = run(); torch.cuda.synchronize()
+            kernels = be.profiler_report(); be.profiler_enable(False)
+            stats1 = be.select_stats()
+            n, fused_batches = q.result_size, q.fused_batches
+            dims, valids, _ = q.fetch()
+            q.release()
+            head = [bytes(d[:w * min(n, 1000000)]) for d, w in zip(dims, (4, 2, 4, 16))] + [bytes(v[:min(n, 1000000)]) for v in valids]
+            del dims, valids
+            check = "first"
+            if not fused:
+                first[limit] = (n, head)
+            else:
+                check = "ok" if first[limit] == (n, head) else "MISMATCH against the ordinary sequence"
+            kernel_ms = sum(ms for c, ms in kernels.values())
+            row = {"config": "select", "limit": limit, "path": "extension" if fused else "ordinary", "rows": rows, "batches": len(vps),
+                   "batch_rows": batch_rows, "result_rows": n, "fused_batches": fused_batches, "check": check,
+                   "tiles_scanned": stats1["tiles"] - stats0["tiles"], "ms_per_step": dt * 1e3, "ms_per_1B_rows": dt * 1e3 * 1e9 / rows,
+                   "kernel_ms_per_step": kernel_ms, "kernel_ms_per_1B_rows": kernel_ms * 1e9 / rows,
+                   "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}
+            if limit < 0 and kernel_ms > 0:
+                algo = rows * col_bytes + n * row_bytes
+                row["algorithmic_bytes"] = algo
+                row["algorithmic_GBps_of_kernel_time"] = algo / (kernel_ms * 1e-3) / 1e9
+                row["frac_of_8TBps"] = row["algorithmic_GBps_of_kernel_time"] / 8000.0
+            out.append(row)
+    return out
+
+
 def wide_key_legs(be, dev, which, rows, batch_rows=1 << 26, steps=3):
     """Sort + Reduce over group keys in dimension slots of 8 and 16 bytes (rows of such a query exist when Sort arrives: a
     transform into a wide slot runs at once), through the C++ driver in the Go call order, COUNT(*):
@@ -548,6 +614,9 @@ def main():
     if "c4" in which: res += c4(be, dev, 1 << 26, 200_000)
     if "c4spec" in which: res += c4_spec(be, dev, int(float(os.environ.get("C4_ROWS", "1e9"))), int(float(os.environ.get("C4_KEYS", "5e7"))))
     if "trips" in which: res += trips_leg(be, dev, int(float(os.environ.get("TRIPS_ROWS", "1e9"))))
+    if "select" in which:  # SELECT_BATCH_ROWS / SELECT_LIMITS (comma separated, -1 = none): other batch sizes, fewer limits
+        res += select_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
+                          limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
     for leg in ("c3int64", "uuid"):
         if leg in which: res += wide_key_legs(be, dev, leg, int(float(os.environ.get("WIDE_ROWS", str(1 << 28)))))
     if "c3sortfloat" in which: res += sort_float_leg(be, dev, int(float(os.environ.get("SORT_FLOAT_ROWS", "1e9"))))
