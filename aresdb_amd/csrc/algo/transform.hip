@@ -5,9 +5,9 @@
 // One DeferState per device, one mutex (DeferLock); nothing below synchronises a stream while it holds the lock (late
 // launches that the host believes done are synchronised after the unlock: t_syncAfterUnlock).  The things a call may
 // DEFINE instead of doing:
-//   * pending[(device, stream)]   root transforms of the hot shape, one queue per stream, launched together
+//   * pending[stream]             root transforms of the hot shape, one queue per stream, launched together
 //                                 (transform_multi_kernel) or consumed by HashReduce's fused scan;
-//   * limbo[(device, stream)]     a queue HashReduce consumed: its outputs were never written, it stays launchable until
+//   * limbo[stream]               a queue HashReduce consumed: its outputs were never written, it stays launchable until
 //                                 the stream's next InitIndexVector (begin_batch) or until its outputs are freed;
 //   * journals[index vector]      the hot-shape filters applied to the vector since InitIndexVector: what the fused scan
 //                                 replays instead of reading the vector;
@@ -17,7 +17,7 @@
 //   * fills[first byte]           a buffer defined as a repeated 4- / 8-byte pattern (constant measures, the hash vector
 //                                 of a query without dimensions);
 //   * (hash_reduce_lds.hip)       measure rows defined by a table image ("lazy values");
-//   * expansions[(device, stream)] run-length encoded (mode-3) columns of an archive batch, decoded ONCE per batch into a
+//   * expansions[stream]          run-length encoded (mode-3) columns of an archive batch, decoded ONCE per batch into a
 //                                 stream temporary laid out like a mode-2 column; the hot-shape machinery below (row-space
 //                                 filters, queued transforms, the fused scans) then reads the copy.  Every definition that
 //                                 reads a copy keeps it alive (`keep`); the per-batch cache dies at the stream's next
@@ -81,7 +81,7 @@ namespace ares {
 // ---------------------------------------------------------------------------------------------
 
 // ---------------------------------------------------------------------------------------------
-// cross-call fusion: root transforms are queued per (device, stream) and launched together
+// cross-call fusion: root transforms are queued per stream and launched together
 // ---------------------------------------------------------------------------------------------
 // Contract and flush points: include/ares_extensions.h.  A queue holds jobs that share the index
 // vector and length; a job whose buffers overlap a queued job's (read-after-write or
@@ -95,6 +95,21 @@ struct ByteRange {
   const uint8_t *lo, *hi;
   bool overlaps(const ByteRange &o) const { return lo < o.hi && o.lo < hi; }
 };
+ByteRange range_of(const void *ptr, size_t bytes) {  // (a range of no bytes counts as its first byte)
+  const uint8_t *lo = static_cast<const uint8_t *>(ptr);
+  return ByteRange{lo, lo + (bytes ? bytes : 1)};
+}
+// the byte ranges a hot-shape operand's column occupies: visit(values) and, where the column has them, visit(validity bits)
+template <typename Visit>
+void column_ranges(const FastOperands &f, uint32_t colRows, Visit &&visit) {
+  visit(range_of(f.vals, fast_value_bytes(f, colRows)));
+  if (f.nulls) visit(range_of(f.nulls, (static_cast<uint64_t>(colRows) + f.bitOff + 7) / 8 + 2));
+}
+bool column_overlaps(const FastOperands &f, uint32_t colRows, const ByteRange &r) {
+  bool hit = false;
+  column_ranges(f, colRows, [&](const ByteRange &c) { hit = hit || c.overlaps(r); });
+  return hit;
+}
 struct PendingQueue {
   MultiJobs jobs;
   uint32_t colRows[kMaxMultiJobs];  // rows of each job's source column
@@ -160,7 +175,6 @@ void order_before_caller(hipStream_t producer) {
 // HashReduce can re-derive the survivors from the source columns instead of reading index, dimension
 // and measure vectors.  Any other writer of the index vector invalidates the entry.
 struct FilterJournal {
-  int device;
   hipStream_t stream;
   uint32_t start;
   int n0;
@@ -216,18 +230,33 @@ struct PredictedFilter {
   int count = 0;
   std::shared_ptr<StreamBuffer> bits;
 };
+// The workspace of a two-phase compaction (tile counts, filter_scan_kernel, one filter_compact_kernel per pass), in one
+// stream temporary of bytes() bytes:
+//   [total, error, one ticket per pass, pad to 64 bytes][tile counts][tile offsets + 1][loaded x passes][extra words]
+// pass 0 compacts the index vector, pass k the k-th RecordID vector; the extra words are the caller's.
+struct CompactSpace {
+  uint32_t *words = nullptr;
+  int tiles = 0, passes = 1;
+  static size_t bytes(int tiles, int passes, size_t extraWords) {
+    return 64 + 4 * (static_cast<size_t>(tiles) * (2 + passes) + 1 + extraWords);
+  }
+  uint32_t *total() const { return words; }  // {survivors, error}: read back together
+  uint32_t *error() const { return words + 1; }
+  unsigned int *tickets() const { return words + 2; }
+  uint32_t *tileCounts() const { return words + 16; }
+  uint32_t *tileOffsets() const { return tileCounts() + tiles; }
+  uint32_t *loaded() const { return tileOffsets() + tiles + 1; }
+  uint32_t *extra() const { return loaded() + static_cast<size_t>(tiles) * passes; }
+};
 struct PendingCompact {
-  int device;
   hipStream_t stream;
   uint32_t *idx;
   const uint8_t *pred;
-  int n, pad, tiles;
+  int n, pad;
   bool virtualIdx;
-  std::shared_ptr<StreamBuffer> ws;  // [total, error, ticket ...][tile counts][tile offsets + 1][loaded]
-  unsigned int *ticket;
-  uint32_t *error, *tileOffsets, *loaded;
-  uint32_t *tileCounts = nullptr, *total = nullptr;  // not null: the scan of the tile counts has not run yet
-  // row-space form (todo not empty: the fields from `pred` to `total` are unused).  The index vector holds
+  std::shared_ptr<StreamBuffer> ws;  // what `space` lies in
+  CompactSpace space;                // tile counts filled in (filter_pred_kernel); their scan has not run yet
+  // row-space form (todo not empty: the fields from `pred` to `space` are unused).  The index vector holds
   // iota(0 .. n0) — virtual or written — with the first `applied` filters of the journal applied; `todo` are the filters
   // counted since, in call order; `bits` the survivors after the last of them, in row space (one 16-bit word per lane and tile).
   std::vector<LazyFilter> todo;
@@ -255,7 +284,6 @@ struct FilterHistory {
 // filter and transform kernels that consume them compute rows = position instead of loading 4 bytes
 // per row; any other use (every flush point) materialises them first.
 struct PendingIota {
-  int device;
   hipStream_t stream;
   uint32_t start;
   int n;
@@ -272,7 +300,6 @@ struct PendingIota {
 // bytes would be (Reduce over zero dimensions) never makes anybody write them; every other reader, copy or flush
 // point writes them first; a free or an overwrite retires them.
 struct PendingFill {
-  int device;
   hipStream_t stream;
   size_t bytes;
   uint64_t pattern;
@@ -286,7 +313,6 @@ struct PendingFill {
 // Sort over a dimension vector whose batch rows are still pending transforms (define_lazy_sort), and — once `reduced` —
 // the Reduce that consumed it together with them (fuse_pending_into_sort_reduce)
 struct PendingSort {
-  int device;
   hipStream_t stream;
   DimensionVector keys;
   int length;
@@ -366,34 +392,41 @@ namespace {
 // An event queried after its stream was destroyed is a use after free inside the ROCm 7.x runtime — see FenceEvent in
 // mem/memory.hip.)
 struct ErrorCheck {
-  int device;
   hipStream_t stream;
   hipEvent_t done;
   uint32_t *pinned;
   std::shared_ptr<StreamBuffer> ws;  // keeps the error word alive until the copy has run
 };
 
+// Everything in here belongs to ONE device (`device`): entries are only ever made under a DeferLock of that device, so
+// nothing below carries a device number of its own.
 struct DeferState {
   std::mutex mutex;
-  std::map<std::pair<int, hipStream_t>, PendingQueue> pending;  // root transforms queued per (device, stream)
-  std::map<std::pair<int, hipStream_t>, PendingQueue> limbo;    // queues a HashReduce consumed on the fly
+  int device = -1;                               // set once, by state_of
+  std::map<hipStream_t, PendingQueue> pending;  // root transforms queued per stream
+  std::map<hipStream_t, PendingQueue> limbo;    // queues a HashReduce consumed on the fly
   std::map<const uint32_t *, FilterJournal> journals;
   std::map<const uint32_t *, PendingCompact> compactions;
-  std::map<std::pair<int, hipStream_t>, FilterHistory> filterHistory;
+  std::map<hipStream_t, FilterHistory> filterHistory;
   uint64_t filterGeneration = 0;
   std::map<uint32_t *, PendingIota> iotas;
   std::map<uint8_t *, PendingFill> fills;  // by first byte; ranges never overlap
   std::map<const uint32_t *, PendingSort> sorts;  // by index vector
-  std::map<std::pair<int, hipStream_t>, std::vector<RunExpansion>> expansions;  // decoded run-length columns of the stream's batch
+  std::map<hipStream_t, std::vector<RunExpansion>> expansions;  // decoded run-length columns of the stream's batch
   std::vector<ErrorCheck> errorChecks;
   std::vector<uint32_t *> errorSlots;  // recycled pinned words
   bool errorSeen = false;              // a check that was settled outside an entry point failed: the next poll reports it
 };
 constexpr int kMaxDevices = 64;
 DeferState &state_of(int device) {
-  static DeferState states[kMaxDevices];
+  static struct States {
+    DeferState of[kMaxDevices];
+    States() {
+      for (int d = 0; d < kMaxDevices; d++) of[d].device = d;
+    }
+  } states;
   if (device < 0 || device >= kMaxDevices) throw std::invalid_argument("device index out of range");
-  return states[device];
+  return states.of[device];
 }
 DeferLock::DeferLock(int device) : lock(state_of(device).mutex, std::defer_lock) {
   {
@@ -404,9 +437,8 @@ DeferLock::DeferLock(int device) : lock(state_of(device).mutex, std::defer_lock)
 }
 
 // caller holds the device's DeferLock
-void watch_error_word(int device, hipStream_t stream, const uint32_t *errorDev, std::shared_ptr<StreamBuffer> ws) {
+void watch_error_word(hipStream_t stream, const uint32_t *errorDev, std::shared_ptr<StreamBuffer> ws) {
   ErrorCheck c;
-  c.device = device;
   c.stream = stream;
   c.ws = std::move(ws);
   if (!t_state->errorSlots.empty()) {
@@ -422,24 +454,77 @@ void watch_error_word(int device, hipStream_t stream, const uint32_t *errorDev, 
   t_state->errorChecks.push_back(std::move(c));
 }
 
+// caller holds the device's DeferLock: check i has landed (its event is done, or its stream is idle).  The event goes, the
+// pinned word is recycled, the last check takes the slot; true when the compaction reported a failure
+bool retire_error_check(size_t i) {
+  ErrorCheck &c = t_state->errorChecks[i];
+  const bool failed = *c.pinned != 0;
+  (void)hipEventDestroy(c.done);
+  t_state->errorSlots.push_back(c.pinned);
+  t_state->errorChecks[i] = std::move(t_state->errorChecks.back());
+  t_state->errorChecks.pop_back();
+  return failed;
+}
+
 // caller holds the device's DeferLock; throws when a finished lazy compaction reported a failure
-void poll_error_words(int device) {
+void poll_error_words() {
   bool failed = t_state->errorSeen;
   t_state->errorSeen = false;
   for (size_t i = 0; i < t_state->errorChecks.size();) {
-    ErrorCheck &c = t_state->errorChecks[i];
-    if (c.device == device && hipEventQuery(c.done) == hipSuccess) {
-      failed = failed || *c.pinned != 0;
-      (void)hipEventDestroy(c.done);
-      t_state->errorSlots.push_back(c.pinned);
-      t_state->errorChecks[i] = std::move(t_state->errorChecks.back());
-      t_state->errorChecks.pop_back();
+    if (hipEventQuery(t_state->errorChecks[i].done) == hipSuccess) {
+      failed = retire_error_check(i) || failed;
     } else {
       (void)hipGetLastError();
       i++;
     }
   }
   if (failed) throw AlgorithmError("ERROR: filter: compaction wait timed out (reported by a deferred compaction)");
+}
+
+// tiles of filter_pred_kernel's geometry that n predicate bytes span, counted in quads from `pad` bytes below the first
+int pred_tiles(int n, int pad) {
+  const int64_t numQuads = (static_cast<int64_t>(n) + pad + 3) / 4;
+  return static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
+}
+// lays a compaction's workspace out over `ws` (CompactSpace::bytes of the same three numbers) and clears it: one fill
+// for head, counts and flags
+CompactSpace clear_compact_space(const StreamBuffer &ws, int tiles, int passes, size_t extraWords, hipStream_t stream) {
+  CompactSpace cs;
+  cs.words = ws.as<uint32_t>();
+  cs.tiles = tiles;
+  cs.passes = passes;
+  hip_check(hipMemsetAsync(cs.words, 0, CompactSpace::bytes(tiles, passes, extraWords), stream), "hipMemsetAsync");
+  return cs;
+}
+// The tile counts of `pred` are in place: their scan, then the chain-free in-place compaction of the index vector
+// (virtualIdx: it is iota(0 .. n) and not written — nothing is read from it) and of every RecordID vector.
+void launch_compaction(const CompactSpace &cs, const uint8_t *pred, uint32_t *idx, bool virtualIdx, RecordID **recordIDVectors, int pad, int n,
+                       hipStream_t stream) {
+  ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, stream, cs.tileCounts(), cs.tileOffsets(), cs.tiles, cs.total());
+  const int cgrid = capped_grid((cs.tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
+  for (int pass = 0; pass < cs.passes; pass++) {
+    CompactWorkspace cw;
+    cw.ticket = cs.tickets() + pass;
+    cw.error = cs.error();
+    cw.tileOffsets = cs.tileOffsets();
+    cw.loaded = cs.loaded() + static_cast<size_t>(cs.tiles) * pass;
+    if (pass == 0 && virtualIdx)
+      ARES_LAUNCH("filter_compact_kernel<iota>", (filter_compact_kernel<uint32_t, true>), cgrid, kBlock, stream, pred, idx, 0u, pad, cw, n,
+                  cs.tiles);
+    else if (pass == 0)
+      ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, stream, pred, idx, 0u, pad, cw, n,
+                  cs.tiles);
+    else
+      ARES_LAUNCH("filter_compact_kernel<rid>", (filter_compact_kernel<uint64_t, false>), cgrid, kBlock, stream, pred,
+                  reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), 0u, pad, cw, n, cs.tiles);
+  }
+}
+// ... and what an eager caller ends with: the survivor count, or the compaction's bounded wait timed out
+int read_compaction_total(const CompactSpace &cs, hipStream_t stream) {
+  uint32_t result[2] = {0, 0};  // {survivors, error}
+  read_back_u32(cs.total(), result, 2, stream);
+  if (result[1]) throw AlgorithmError("ERROR: filter: compaction wait timed out");
+  return static_cast<int>(result[0]);
 }
 
 // caller holds the device's DeferLock and has selected the device: runs the pending compaction of `idx` (if
@@ -454,22 +539,9 @@ void run_compaction(const uint32_t *idx) {
     replay_lazy_filters(c);
     return;
   }
-  mem_note_write(c.device, c.idx, 4ull * static_cast<size_t>(c.n));
-  CompactWorkspace cw;
-  cw.ticket = c.ticket;
-  cw.error = c.error;
-  cw.tileOffsets = c.tileOffsets;
-  cw.loaded = c.loaded;
-  const int cgrid = capped_grid((c.tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
-  if (c.tileCounts)
-    ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, c.stream, c.tileCounts, c.tileOffsets, c.tiles, c.total);
-  if (c.virtualIdx)
-    ARES_LAUNCH("filter_compact_kernel<iota>", (filter_compact_kernel<uint32_t, true>), cgrid, kBlock, c.stream, c.pred, c.idx, 0u,
-                c.pad, cw, c.n, c.tiles);
-  else
-    ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, c.stream, c.pred, c.idx, 0u,
-                c.pad, cw, c.n, c.tiles);
-  watch_error_word(c.device, c.stream, c.error, c.ws);
+  mem_note_write(t_state->device, c.idx, 4ull * static_cast<size_t>(c.n));
+  launch_compaction(c.space, c.pred, c.idx, c.virtualIdx, nullptr, c.pad, c.n, c.stream);
+  watch_error_word(c.stream, c.space.error(), c.ws);
   order_before_caller(c.stream);
   // (c.ws is released to the stream's cache when the last copy of the shared_ptr goes: behind the launch
   // and the copy of the error word)
@@ -480,62 +552,44 @@ void run_compaction(const uint32_t *idx) {
 // caller holds the device's DeferLock and has selected the device
 void replay_lazy_filters(const PendingCompact &c) {
   bool virtualIdx = c.virtualIdx;
-  mem_note_write(c.device, c.idx, 4ull * static_cast<size_t>(c.n0));
+  mem_note_write(t_state->device, c.idx, 4ull * static_cast<size_t>(c.n0));
   for (const LazyFilter &L : c.todo) {
     const int n = L.rowsBefore;
     if (n <= 0) break;
-    mem_note_write(c.device, L.pred, static_cast<size_t>(n));
+    mem_note_write(t_state->device, L.pred, static_cast<size_t>(n));
     FastOperands f = L.f;
     f.idx = virtualIdx ? nullptr : c.idx;
     f.pad = static_cast<int>(reinterpret_cast<uintptr_t>(L.pred) & 3);
-    const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
-    const int tiles = static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
-    const size_t head = 64;
-    const size_t words = static_cast<size_t>(tiles) * 3 + 1;  // [tile counts][tile offsets + 1][loaded]
-    auto wsBuf = std::make_shared<StreamBuffer>(head + 4 * words, c.stream);
-    uint32_t *w = wsBuf->as<uint32_t>();
-    uint32_t *total = w, *error = w + 1;
-    uint32_t *tileCounts = w + 16, *tileOffsets = tileCounts + tiles, *loaded = tileOffsets + tiles + 1;
-    hip_check(hipMemsetAsync(w, 0, head + 4 * words, c.stream), "hipMemsetAsync");
-    ARES_LAUNCH("filter_pred_kernel", filter_pred_kernel, capped_grid(tiles, 256 * 16), kBlock, c.stream, f, L.pred, tileCounts, n, tiles,
+    const int tiles = pred_tiles(n, f.pad);
+    auto wsBuf = std::make_shared<StreamBuffer>(CompactSpace::bytes(tiles, 1, 0), c.stream);
+    const CompactSpace cs = clear_compact_space(*wsBuf, tiles, 1, 0, c.stream);
+    ARES_LAUNCH("filter_pred_kernel", filter_pred_kernel, capped_grid(tiles, 256 * 16), kBlock, c.stream, f, L.pred, cs.tileCounts(), n, tiles,
                 static_cast<uint32_t *>(nullptr));
-    ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, c.stream, tileCounts, tileOffsets, tiles, total);
-    CompactWorkspace cw;
-    cw.ticket = w + 2;
-    cw.error = error;
-    cw.tileOffsets = tileOffsets;
-    cw.loaded = loaded;
-    const int cgrid = capped_grid((tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
-    if (virtualIdx)
-      ARES_LAUNCH("filter_compact_kernel<iota>", (filter_compact_kernel<uint32_t, true>), cgrid, kBlock, c.stream, L.pred, c.idx, 0u, f.pad,
-                  cw, n, tiles);
-    else
-      ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, c.stream, L.pred, c.idx, 0u, f.pad, cw,
-                  n, tiles);
-    watch_error_word(c.device, c.stream, error, wsBuf);
+    launch_compaction(cs, L.pred, c.idx, virtualIdx, nullptr, f.pad, n, c.stream);
+    watch_error_word(c.stream, cs.error(), wsBuf);
     virtualIdx = false;
   }
   order_before_caller(c.stream);
 }
 
+// (range_of counts a range of no bytes as its first byte: a filter booked over no rows, or a column of no rows, would hit on
+// that byte — neither is ever booked, and a hit only makes a caller launch or hold something early)
 bool compaction_touches(const PendingCompact &c, const ByteRange &r) {
   if (!c.todo.empty()) {  // index vector, every predicate vector and every column a replay would read
-    const ByteRange ri{reinterpret_cast<const uint8_t *>(c.idx), reinterpret_cast<const uint8_t *>(c.idx) + 4ull * c.n0};
-    bool hit = ri.overlaps(r);
-    for (const LazyFilter &L : c.todo) {
-      const ByteRange rp{L.pred, L.pred + L.rowsBefore};
-      const ByteRange rv{reinterpret_cast<const uint8_t *>(L.f.vals), reinterpret_cast<const uint8_t *>(L.f.vals) + fast_value_bytes(L.f, L.colRows)};
-      hit = hit || rp.overlaps(r) || rv.overlaps(r);
-      if (L.f.nulls) {
-        const ByteRange rn{L.f.nulls, L.f.nulls + (static_cast<uint64_t>(L.colRows) + L.f.bitOff + 7) / 8 + 2};
-        hit = hit || rn.overlaps(r);
-      }
-    }
+    bool hit = range_of(c.idx, 4ull * c.n0).overlaps(r);
+    for (const LazyFilter &L : c.todo) hit = hit || range_of(L.pred, L.rowsBefore).overlaps(r) || column_overlaps(L.f, L.colRows, r);
     return hit;
   }
-  const ByteRange ri{reinterpret_cast<const uint8_t *>(c.idx), reinterpret_cast<const uint8_t *>(c.idx) + 4ull * c.n};
-  const ByteRange rp{c.pred, c.pred + c.n};
-  return ri.overlaps(r) || rp.overlaps(r);
+  return range_of(c.idx, 4ull * c.n).overlaps(r) || range_of(c.pred, c.n).overlaps(r);
+}
+
+// One fast transform on a kernel of its own: the quads are counted from where the sink's validity bytes are 4-byte aligned
+// (a measure has none).
+void launch_fast_transform(FastOperands f, const SinkD &s, int n, hipStream_t stream) {
+  f.pad = s.type == SINK_MEASURE ? 0 : static_cast<int>(reinterpret_cast<uintptr_t>(s.nulls) & 3);
+  const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
+  const int64_t tiles = (numQuads + kBlock * kTQ - 1) / (kBlock * kTQ);
+  ARES_LAUNCH("transform_fast_kernel", transform_fast_kernel, capped_grid(tiles, 256 * 16), kBlock, stream, f, s, n, numQuads);
 }
 
 // caller holds the device's DeferLock and has selected the device.  inOrder: the launch is part of the
@@ -546,16 +600,13 @@ void launch_queue(hipStream_t stream, PendingQueue &q, bool inOrder = false) {
   const bool syncAfter = q.overWait && !inOrder;
   q.overWait = false;
   if (q.idx) run_compaction(q.idx);  // the transforms read the compacted index vector
-  const int64_t numQuads = (static_cast<int64_t>(q.n) + 3) / 4;
-  const int64_t tiles = (numQuads + kBlock * kTQ - 1) / (kBlock * kTQ);
   if (q.jobs.count == 1) {
     FastOperands f = q.jobs.f[0];
     f.idx = q.idx;
-    f.pad = q.jobs.s[0].type == SINK_MEASURE ? 0 : static_cast<int>(reinterpret_cast<uintptr_t>(q.jobs.s[0].nulls) & 3);
-    const int64_t nq = (static_cast<int64_t>(q.n) + f.pad + 3) / 4;
-    const int64_t t1 = (nq + kBlock * kTQ - 1) / (kBlock * kTQ);
-    ARES_LAUNCH("transform_fast_kernel", transform_fast_kernel, capped_grid(t1, 256 * 16), kBlock, stream, f, q.jobs.s[0], q.n, nq);
+    launch_fast_transform(f, q.jobs.s[0], q.n, stream);
   } else {
+    const int64_t numQuads = (static_cast<int64_t>(q.n) + 3) / 4;
+    const int64_t tiles = (numQuads + kBlock * kTQ - 1) / (kBlock * kTQ);
     ARES_LAUNCH("transform_multi_kernel", transform_multi_kernel, capped_grid(tiles, 256 * 16), kBlock, stream, q.jobs, q.idx,
                 q.n, numQuads);
   }
@@ -571,12 +622,12 @@ void launch_queue(hipStream_t stream, PendingQueue &q, bool inOrder = false) {
 }
 
 // caller holds the device's DeferLock.  Launches the skipped transforms of every limbo entry of the device
-// (all = true) or of those whose outputs overlap `range`, and forgets the entries.
-bool materialize_limbo(int device, const ByteRange *range, ReleaseSet *released) {
+// (range == nullptr) or of those whose outputs overlap `range`, and forgets the entries.
+bool materialize_limbo(const ByteRange *range, ReleaseSet *released) {
   bool any = false;
   for (auto it = t_state->limbo.begin(); it != t_state->limbo.end();) {
-    bool hit = it->first.first == device;
-    if (hit && range) {
+    bool hit = true;
+    if (range) {
       hit = false;
       for (const ByteRange &w : it->second.writes) hit = hit || w.overlaps(*range);
     }
@@ -586,8 +637,8 @@ bool materialize_limbo(int device, const ByteRange *range, ReleaseSet *released)
       any = true;
     } else if (hit) {
       it->second.overWait = true;  // the host believes this work is long done
-      launch_queue(it->first.second, it->second);
-      if (released) released->add(it->first.second);
+      launch_queue(it->first, it->second);
+      if (released) released->add(it->first);
       it = t_state->limbo.erase(it);
       any = true;
     } else {
@@ -595,6 +646,18 @@ bool materialize_limbo(int device, const ByteRange *range, ReleaseSet *released)
     }
   }
   return any;
+}
+
+// caller holds the device's DeferLock.  A limbo entry dies: its skipped outputs will never be written.  The compaction only it
+// would need goes with it, the blocks held for its stream may go (`released`; null: the caller releases the stream's
+// tag anyway, as begin_batch and hook_on_stream_destroy do), and what a Reduce that consumed the queue left defined cannot be replayed any more.  Returns the next entry.
+std::map<hipStream_t, PendingQueue>::iterator drop_limbo(std::map<hipStream_t, PendingQueue>::iterator it, ReleaseSet *released) {
+  if (it->second.idx) t_state->compactions.erase(it->second.idx);
+  if (released) released->add(it->first);
+  const uint32_t *sortIdx = it->second.sortIdx;
+  it = t_state->limbo.erase(it);
+  if (sortIdx) drop_sort(sortIdx);
+  return it;
 }
 }  // namespace
 
@@ -608,18 +671,31 @@ static void launch_init_index(uint32_t *indexVector, uint32_t start, int n, hipS
   order_before_caller(stream);  // (a lazy iota written at another stream's flush point)
 }
 
-// ---- lazy fills -----------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void fill_pattern_kernel(uint8_t *dst, size_t units, uint64_t pattern, int unit) {
-  for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < units; i += static_cast<size_t>(gridDim.x) * kBlock) {
-    if (unit == 8) reinterpret_cast<uint64_t *>(dst)[i] = pattern;
-    else reinterpret_cast<uint32_t *>(dst)[i] = static_cast<uint32_t>(pattern);
-  }
+// caller holds the device's DeferLock: the entry of `indexVector` when the vector is a lazy iota(0 .. n) that no Sort has
+// been defined over, or null.  (What `consumed` must be is the caller's business.)
+static PendingIota *lazy_iota(const uint32_t *indexVector, int n) {
+  auto it = t_state->iotas.find(const_cast<uint32_t *>(indexVector));
+  if (it == t_state->iotas.end() || it->second.start != 0 || it->second.n != n || it->second.sorted) return nullptr;
+  return &it->second;
 }
 
+// caller holds the device's DeferLock and has selected the device: what the entry defines its vector to hold is written
+// now — the iota or, once `sorted`, what the lazily defined Sort leaves (materialize_sort: the entry goes with the
+// definition).  Returns where a loop over the iotas goes on.
+static std::map<uint32_t *, PendingIota>::iterator write_iota(std::map<uint32_t *, PendingIota>::iterator it) {
+  if (it->second.sorted) {
+    materialize_sort(it->first);
+    return t_state->iotas.begin();
+  }
+  launch_init_index(it->first, it->second.start, it->second.n, it->second.stream);
+  return t_state->iotas.erase(it);
+}
+
+// ---- lazy fills -----------------------------------------------------------------------------------------
 // caller holds the device's DeferLock and has selected the device
 static void launch_fill(uint8_t *dst, const PendingFill &f) {
   if (f.bytes == 0 || f.sortIdx) return;  // (a sort's marker is not a pattern: materialize_sort)
-  mem_note_write(f.device, dst, f.bytes);
+  mem_note_write(t_state->device, dst, f.bytes);
   const size_t units = f.bytes / static_cast<size_t>(f.unit);
   // a fill whose defining stream is gone is written on the caller's stream (or, from a libmem.so hook, on the null stream)
   const hipStream_t stream = f.streamGone ? (t_callStream.known ? t_callStream.stream : nullptr) : f.stream;
@@ -630,10 +706,10 @@ static void launch_fill(uint8_t *dst, const PendingFill &f) {
 
 // caller holds the device's DeferLock: every lazy fill of the device (r == nullptr) or those that overlap r are
 // written now
-static void materialize_fills(int device, const ByteRange *r, std::vector<hipStream_t> *touched = nullptr) {
+static void materialize_fills(const ByteRange *r, std::vector<hipStream_t> *touched = nullptr) {
   for (auto it = t_state->fills.begin(); it != t_state->fills.end();) {
-    const ByteRange v{it->first, it->first + it->second.bytes};
-    if (it->second.device == device && it->second.sortIdx) {
+    const ByteRange v = range_of(it->first, it->second.bytes);
+    if (it->second.sortIdx) {
       // a buffer a lazily defined Sort (+ Reduce) would write: only for somebody who looks at these very bytes
       if (r && v.overlaps(*r)) {
         if (touched) touched->push_back(it->second.stream);
@@ -642,7 +718,7 @@ static void materialize_fills(int device, const ByteRange *r, std::vector<hipStr
       } else {
         ++it;
       }
-    } else if (it->second.device == device && (!r || v.overlaps(*r))) {
+    } else if (!r || v.overlaps(*r)) {
       launch_fill(it->first, it->second);
       if (touched) touched->push_back(it->second.stream);
       it = t_state->fills.erase(it);
@@ -655,12 +731,12 @@ static void materialize_fills(int device, const ByteRange *r, std::vector<hipStr
 // caller holds the device's DeferLock: [r.lo, r.hi) is freed (`gone`) or about to be overwritten.  Lazy fills inside
 // it die; one that sticks out at an end is shortened (on a pattern boundary); one that is cut in the middle, or off
 // a pattern boundary, is written first.
-static void retire_fills(int device, const ByteRange &r, bool gone) {
+static void retire_fills(const ByteRange &r, bool gone) {
   for (auto it = t_state->fills.begin(); it != t_state->fills.end();) {
     uint8_t *lo = it->first;
     PendingFill f = it->second;
     const uint8_t *hi = lo + f.bytes;
-    if (f.device != device || !(lo < r.hi && r.lo < hi)) {
+    if (!(lo < r.hi && r.lo < hi)) {
       ++it;
       continue;
     }
@@ -733,7 +809,7 @@ static void materialize_sort(const uint32_t *indexVector) {
   if (s.reduced && s.fromVectors) {
     // (the rows exist: nothing to launch first)
   } else if (s.reduced) {
-    auto lim = t_state->limbo.find({s.device, s.stream});
+    auto lim = t_state->limbo.find(s.stream);
     if (lim != t_state->limbo.end()) {
       lim->second.overWait = true;  // the host believes this work is long done
       launch_queue(s.stream, lim->second);
@@ -746,7 +822,7 @@ static void materialize_sort(const uint32_t *indexVector) {
       launch_fill(s.fillAt, f);
     }
   } else {
-    auto pq = t_state->pending.find({s.device, s.stream});
+    auto pq = t_state->pending.find(s.stream);
     if (pq != t_state->pending.end() && pq->second.jobs.count) {
       if (pq->second.overWait) released.add(s.stream);
       launch_queue(s.stream, pq->second);
@@ -756,7 +832,7 @@ static void materialize_sort(const uint32_t *indexVector) {
   sort_keys_now(s.keys, s.length, s.stream);
   if (s.reduced) (void)reduce_now(s.keys, s.inValues, s.outKeys, s.outValues, s.valueBytes, s.length, s.aggFunc, s.stream);
   order_before_caller(s.stream);
-  released.run(s.device);
+  released.run(t_state->device);
 }
 
 // [dst, dst + bytes) is defined as `pattern` (unit = 4 or 8 bytes) repeated; false = deferral is off, the caller writes
@@ -767,15 +843,15 @@ bool defer_fill(int device, hipStream_t stream, void *dst, size_t bytes, uint64_
   drop_skipped_outputs(device, dst, bytes, nullptr, 0);  // what an earlier HashReduce skipped and would write there is dead
   DeferLock lock(device);
   uint8_t *p = static_cast<uint8_t *>(dst);
-  const ByteRange r{p, p + bytes};
+  const ByteRange r = range_of(p, bytes);
   for (auto &kv : t_state->pending) {  // queued transforms that write into the range come first (call order)
     bool hit = false;
-    if (kv.first.first == device && kv.second.jobs.count)
+    if (kv.second.jobs.count)
       for (const ByteRange &w : kv.second.writes) hit = hit || w.overlaps(r);
-    if (hit) launch_queue(kv.first.second, kv.second);
+    if (hit) launch_queue(kv.first, kv.second);
   }
-  retire_fills(device, r, false);
-  t_state->fills[p] = PendingFill{device, stream, bytes, pattern, unit, false};
+  retire_fills(r, false);
+  t_state->fills[p] = PendingFill{stream, bytes, pattern, unit, false};
   return true;
 }
 
@@ -784,7 +860,7 @@ bool pending_fill_exact(int device, const void *dst, size_t bytes, uint64_t *pat
   if (!defer_available()) return false;
   DeferLock lock(device);
   auto it = t_state->fills.find(const_cast<uint8_t *>(static_cast<const uint8_t *>(dst)));
-  if (it == t_state->fills.end() || it->second.device != device || it->second.bytes != bytes || it->second.sortIdx) return false;
+  if (it == t_state->fills.end() || it->second.bytes != bytes || it->second.sortIdx) return false;
   if (pattern) *pattern = it->second.pattern;
   if (unit) *unit = it->second.unit;
   return true;
@@ -796,7 +872,7 @@ bool pending_fill_tail(int device, const void *base, int width, int length, int 
   DeferLock lock(device);
   const uint8_t *b = static_cast<const uint8_t *>(base), *end = b + static_cast<size_t>(width) * length;
   auto it = t_state->fills.lower_bound(const_cast<uint8_t *>(b));
-  if (it == t_state->fills.end() || it->second.device != device || it->second.unit != width || it->second.sortIdx) return false;
+  if (it == t_state->fills.end() || it->second.unit != width || it->second.sortIdx) return false;
   if (it->first >= end || it->first + it->second.bytes != end || static_cast<size_t>(it->first - b) % static_cast<size_t>(width)) return false;
   *prev = static_cast<int>(static_cast<size_t>(it->first - b) / static_cast<size_t>(width));
   *pattern = it->second.pattern;
@@ -808,8 +884,7 @@ void retire_fills_for_write(int device, const void *ptr, size_t bytes) {
   if (!ptr || bytes == 0 || !defer_available()) return;
   DeferLock lock(device);
   if (t_state->fills.empty()) return;
-  const uint8_t *p = static_cast<const uint8_t *>(ptr);
-  retire_fills(device, ByteRange{p, p + bytes}, false);
+  retire_fills(range_of(ptr, bytes), false);
 }
 
 // [ptr, ptr + bytes) is about to be read by a kernel of the calling entry point
@@ -817,9 +892,8 @@ void materialize_fills_for_read(int device, const void *ptr, size_t bytes) {
   if (!ptr || bytes == 0 || !defer_available()) return;
   DeferLock lock(device);
   if (t_state->fills.empty()) return;
-  const uint8_t *p = static_cast<const uint8_t *>(ptr);
-  const ByteRange r{p, p + bytes};
-  materialize_fills(device, &r);
+  const ByteRange r = range_of(ptr, bytes);
+  materialize_fills(&r);
 }
 
 // true when `indexVector` is defined as iota(0 .. n) and not written yet (InitIndexVector is lazy); consume: the
@@ -827,10 +901,9 @@ void materialize_fills_for_read(int device, const void *ptr, size_t bytes) {
 bool virtual_iota_peek(int device, const uint32_t *indexVector, int n, bool consume) {
   if (!defer_available()) return false;
   DeferLock lock(device);
-  auto it = t_state->iotas.find(const_cast<uint32_t *>(indexVector));
-  if (it == t_state->iotas.end() || it->second.device != device || it->second.start != 0 || it->second.n != n || it->second.sorted) return false;
-  if (consume) it->second.consumed = true;
-  return true;
+  PendingIota *io = lazy_iota(indexVector, n);
+  if (io && consume) io->consumed = true;
+  return io != nullptr;
 }
 
 // an entry point reads (or rewrites) the buffers of a dimension vector with kernels: lazy fills inside them are written
@@ -852,13 +925,7 @@ void materialize_index_vector(int device, const uint32_t *indexVector) {
   if (!indexVector || !defer_available()) return;
   DeferLock lock(device);
   auto it = t_state->iotas.find(const_cast<uint32_t *>(indexVector));
-  if (it == t_state->iotas.end() || it->second.device != device || !it->second.consumed) return;
-  if (it->second.sorted) {  // defined as what Sort leaves: run it
-    materialize_sort(indexVector);
-    return;
-  }
-  launch_init_index(it->first, it->second.start, it->second.n, it->second.stream);
-  t_state->iotas.erase(it);
+  if (it != t_state->iotas.end() && it->second.consumed) write_iota(it);
 }
 
 // limboA/limboB: when given, only the skipped work whose outputs overlap these byte ranges is
@@ -870,23 +937,15 @@ static void flush_deferred_impl(int device, const ByteRange *limboA, const ByteR
   if (limboA) grouped_materialize_for_read(device, limboA->lo, static_cast<size_t>(limboA->hi - limboA->lo));
   if (limboB) grouped_materialize_for_read(device, limboB->lo, static_cast<size_t>(limboB->hi - limboB->lo));
   DeferLock lock(device);
-  poll_error_words(device);
+  poll_error_words();
   // lazy fills (like work a HashReduce skipped, below) are only written for byte ranges the caller reads: they live in
   // measure / hash vectors, which only Sort, Reduce, HashReduce, Expand, HyperLogLog and copies look at
-  if (limboA) materialize_fills(device, limboA);
-  if (limboB) materialize_fills(device, limboB);
+  if (limboA) materialize_fills(limboA);
+  if (limboB) materialize_fills(limboB);
   for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();) {
-    const ByteRange v{reinterpret_cast<const uint8_t *>(it->first), reinterpret_cast<const uint8_t *>(it->first) + 4ull * it->second.n};
+    const ByteRange v = range_of(it->first, 4ull * it->second.n);
     const bool wanted = !it->second.consumed || (limboA && v.overlaps(*limboA)) || (limboB && v.overlaps(*limboB));
-    if (it->second.device == device && wanted && it->second.sorted) {
-      materialize_sort(it->first);
-      it = t_state->iotas.begin();
-    } else if (it->second.device == device && wanted) {
-      launch_init_index(it->first, it->second.start, it->second.n, it->second.stream);
-      it = t_state->iotas.erase(it);
-    } else {
-      ++it;
-    }
+    it = wanted ? write_iota(it) : std::next(it);
   }
   // pending compactions: whoever comes next may read the index vector — except where only work that a
   // HashReduce skipped would read it (the previous batch of the query's other stream): that stays
@@ -899,21 +958,20 @@ static void flush_deferred_impl(int device, const ByteRange *limboA, const ByteR
   };
   for (;;) {
     auto c = t_state->compactions.begin();
-    while (c != t_state->compactions.end() && (c->second.device != device || c->first == exempt || dormant(c->first))) ++c;
+    while (c != t_state->compactions.end() && (c->first == exempt || dormant(c->first))) ++c;
     if (c == t_state->compactions.end()) break;
     run_compaction(c->first);
   }
   ReleaseSet released;
-  for (auto &kv : t_state->pending)
-    if (kv.first.first == device) {
-      if (kv.second.overWait && kv.second.jobs.count) released.add(kv.first.second);
-      launch_queue(kv.first.second, kv.second);
-    }
+  for (auto &kv : t_state->pending) {
+    if (kv.second.overWait && kv.second.jobs.count) released.add(kv.first);
+    launch_queue(kv.first, kv.second);
+  }
   // Work that a HashReduce skipped (limbo) is only launched for byte ranges the caller reads: a full
   // flush from an unrelated call (the next batch's first filter on the query's other stream, say)
   // leaves it alone.
-  if (limboA) materialize_limbo(device, limboA, &released);
-  if (limboB) materialize_limbo(device, limboB, &released);
+  if (limboA) materialize_limbo(limboA, &released);
+  if (limboB) materialize_limbo(limboB, &released);
   released.run(device);
 }
 
@@ -931,24 +989,14 @@ void flush_deferred_for_vector(int device, const DimensionVector &v, const void 
 // streams: batch k's skipped transforms target the buffer batch k+1 reduces into).
 void drop_skipped_outputs(int device, const void *a, size_t aBytes, const void *b, size_t bBytes) {
   if (!fuse_available()) return;
-  const ByteRange ra{static_cast<const uint8_t *>(a), static_cast<const uint8_t *>(a) + (aBytes ? aBytes : 1)};
-  const ByteRange rb{static_cast<const uint8_t *>(b), static_cast<const uint8_t *>(b) + (bBytes ? bBytes : 1)};
+  const ByteRange ra = range_of(a, aBytes), rb = range_of(b, bBytes);
   ReleaseSet released;
   {
     DeferLock lock(device);
     for (auto it = t_state->limbo.begin(); it != t_state->limbo.end();) {
       bool hit = false;
-      if (it->first.first == device)
-        for (const ByteRange &w : it->second.writes) hit = hit || w.overlaps(ra) || w.overlaps(rb);
-      if (hit) {
-        if (it->second.idx) t_state->compactions.erase(it->second.idx);
-        released.add(it->first.second);
-        const uint32_t *sortIdx = it->second.sortIdx;
-        it = t_state->limbo.erase(it);
-        if (sortIdx) drop_sort(sortIdx);  // (what its Reduce left defined cannot be replayed any more)
-      } else {
-        ++it;
-      }
+      for (const ByteRange &w : it->second.writes) hit = hit || w.overlaps(ra) || w.overlaps(rb);
+      it = hit ? drop_limbo(it, &released) : std::next(it);
     }
   }
   released.run(device);
@@ -956,8 +1004,7 @@ void drop_skipped_outputs(int device, const void *a, size_t aBytes, const void *
 
 // for an entry point that reads exactly [a, a + aBytes) and [b, b + bBytes) of device memory
 void flush_deferred_for_inputs(int device, const void *a, size_t aBytes, const void *b, size_t bBytes) {
-  const ByteRange ra{static_cast<const uint8_t *>(a), static_cast<const uint8_t *>(a) + (aBytes ? aBytes : 1)};
-  const ByteRange rb{static_cast<const uint8_t *>(b), static_cast<const uint8_t *>(b) + (bBytes ? bBytes : 1)};
+  const ByteRange ra = range_of(a, aBytes), rb = range_of(b, bBytes);
   flush_deferred_impl(device, &ra, &rb);
 }
 
@@ -965,19 +1012,16 @@ void flush_deferred_for_inputs(int device, const void *a, size_t aBytes, const v
 // now (the host has swapped its result buffers), and the new index vector starts a filter journal.
 static void begin_batch(int device, hipStream_t stream, const uint32_t *indexVector, uint32_t start, int n) {
   if (!fuse_available()) return;
-  bool release = false;
+  bool release = false;  // (no ReleaseSet: this runs once per batch, and a set's first tag is a heap allocation)
   {
     DeferLock lock(device);
-    auto lim = t_state->limbo.find({device, stream});
+    auto lim = t_state->limbo.find(stream);
     if (lim != t_state->limbo.end()) {  // the skipped work of the previous batch dies, and with it the compaction it would need
-      if (lim->second.idx) t_state->compactions.erase(lim->second.idx);
-      const uint32_t *sortIdx = lim->second.sortIdx;
-      t_state->limbo.erase(lim);
-      if (sortIdx) drop_sort(sortIdx);
+      drop_limbo(lim, nullptr);
       release = true;
     }
     t_state->compactions.erase(indexVector);  // the vector is redefined
-    t_state->expansions.erase({device, stream});  // (what still reads a decoded column keeps it alive itself)
+    t_state->expansions.erase(stream);  // (what still reads a decoded column keeps it alive itself)
     {  // ARES_RTC_TRACE (diagnostics): who holds decoded run-length columns when a batch begins
       static int calls = 0;
       if ((++calls & 15) == 0) {
@@ -997,14 +1041,13 @@ static void begin_batch(int device, hipStream_t stream, const uint32_t *indexVec
     }
     drop_sort(indexVector);                   // ... and so is whatever a lazily defined Sort meant it to hold
     {  // the stream's filters of the batch that just ended are what the new batch's are predicted from
-      FilterHistory &h = t_state->filterHistory[{device, stream}];
+      FilterHistory &h = t_state->filterHistory[stream];
       if (!h.current.empty()) {  // (the Sort path opens a second index vector per batch: no filters there, nothing to learn)
         h.previous.swap(h.current);
         h.current.clear();
       }
     }
     FilterJournal j;
-    j.device = device;
     j.stream = stream;
     j.start = start;
     j.n0 = n;
@@ -1064,7 +1107,7 @@ static bool defer_iota(int device, hipStream_t stream, uint32_t *indexVector, ui
   if (!defer_available() || n <= 0) return false;
   DeferLock lock(device);
   drop_sort(indexVector);
-  t_state->iotas[indexVector] = PendingIota{device, stream, start, n};
+  t_state->iotas[indexVector] = PendingIota{stream, start, n};
   return true;
 }
 
@@ -1072,9 +1115,8 @@ static bool defer_iota(int device, hipStream_t stream, uint32_t *indexVector, ui
 // (the caller is about to give the vector real contents)
 static bool virtual_iota(int device, uint32_t *indexVector, int n, bool take) {
   DeferLock lock(device);
-  auto it = t_state->iotas.find(indexVector);
-  if (it == t_state->iotas.end() || it->second.device != device || it->second.start != 0 || it->second.n != n || it->second.sorted) return false;
-  if (take) t_state->iotas.erase(it);
+  if (!lazy_iota(indexVector, n)) return false;
+  if (take) t_state->iotas.erase(indexVector);
   return true;
 }
 
@@ -1084,15 +1126,21 @@ static bool defer_transform(int device, hipStream_t stream, const FastOperands &
   if (!defer_available()) return false;
   DeferLock lock(device);
   // everything pending on OTHER streams of the device is unrelated; only this stream's queue matters
-  PendingQueue &q = t_state->pending[{device, stream}];
-  ByteRange rv{reinterpret_cast<const uint8_t *>(f.vals), reinterpret_cast<const uint8_t *>(f.vals) + fast_value_bytes(f, colRows)};
-  ByteRange rn{f.nulls, f.nulls ? f.nulls + (static_cast<uint64_t>(colRows) + f.bitOff + 7) / 8 + 2 : f.nulls};
-  ByteRange ri{reinterpret_cast<const uint8_t *>(f.idx), reinterpret_cast<const uint8_t *>(f.idx) + (f.idx ? 4ull * n : 0)};
-  ByteRange wv{s.values, s.values + static_cast<uint64_t>(s.width) * n};
-  ByteRange wn{s.nulls, s.nulls ? s.nulls + n : s.nulls};
+  PendingQueue &q = t_state->pending[stream];
+  // what the job reads (the column, the index vector) and writes (the sink's values, its validity bytes)
+  ByteRange reads[3], writes[2];
+  int nr = 0, nw = 0;
+  column_ranges(f, colRows, [&](const ByteRange &c) { reads[nr++] = c; });
+  if (f.idx) reads[nr++] = range_of(f.idx, 4ull * n);
+  writes[nw++] = range_of(s.values, static_cast<uint64_t>(s.width) * n);
+  if (s.nulls) writes[nw++] = range_of(s.nulls, n);
   bool conflict = q.jobs.count == kMaxMultiJobs || (q.jobs.count > 0 && (q.idx != f.idx || q.n != n));
-  for (const ByteRange &w : q.writes) conflict = conflict || w.overlaps(rv) || w.overlaps(rn) || w.overlaps(ri) || w.overlaps(wv) || w.overlaps(wn);
-  for (const ByteRange &r : q.reads) conflict = conflict || r.overlaps(wv) || r.overlaps(wn);
+  for (const ByteRange &w : q.writes) {
+    for (int k = 0; k < nr; k++) conflict = conflict || w.overlaps(reads[k]);
+    for (int k = 0; k < nw; k++) conflict = conflict || w.overlaps(writes[k]);
+  }
+  for (const ByteRange &r : q.reads)
+    for (int k = 0; k < nw; k++) conflict = conflict || r.overlaps(writes[k]);
   if (conflict) launch_queue(stream, q);
   q.idx = f.idx;
   q.n = n;
@@ -1102,75 +1150,13 @@ static bool defer_transform(int device, hipStream_t stream, const FastOperands &
   q.jobs.s[q.jobs.count] = s;
   q.colRows[q.jobs.count] = colRows;
   q.jobs.count++;
-  q.reads.push_back(rv);
-  if (f.nulls) q.reads.push_back(rn);
-  if (f.idx) q.reads.push_back(ri);
-  q.writes.push_back(wv);
-  if (s.nulls) q.writes.push_back(wn);
+  q.reads.insert(q.reads.end(), reads, reads + nr);
+  q.writes.insert(q.writes.end(), writes, writes + nw);
   if (keep) q.keep.push_back(std::move(keep));
   return true;
 }
 
 // ---- run-length encoded columns (archive batches) -------------------------------------------------------------------------
-// rows [0, n) of a mode-3 column — [counts u32 x (runs + 1)][validity bit per run][value per run], row r lives in the run that
-// holds startCount + r (query/iterator.hpp:199-278; locate() of device_model.hpp) — written as [validity bit per row][value
-// per row].  A lane decodes 32 consecutive rows: one binary search, then a walk along the counts; one validity word.
-__global__ __launch_bounds__(kBlock) void expand_runs_kernel(const uint32_t *counts, int numRuns, const uint8_t *nulls, uint32_t bitOff,
-                                                             const uint8_t *values, int step, uint32_t startCount, int n, uint32_t *outNulls,
-                                                             uint8_t *outValues) {
-  // A wavefront decodes 2048 consecutive rows: lane l walks rows [32 l, 32 l + 32) of the tile (values into LDS, row r at word
-  // r + r / 32: the lanes' columns fall into different banks), then the tile leaves the CU as whole lines — lane l stores rows
-  // l, l + 64, ... (the first version stored each lane's 128 bytes where the lane walked: 64 scattered 4-byte stores per
-  // instruction, 0.90 ms per 64 Mi rows instead of 0.1).
-  __shared__ uint32_t sTile[kBlock / 64][2048 + 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t *tile = sTile[wave];
-  const int64_t tiles = (static_cast<int64_t>(n) + 2047) / 2048;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * (kBlock / 64) + wave; t < tiles; t += static_cast<int64_t>(gridDim.x) * (kBlock / 64)) {
-    const int64_t w = t * 64 + lane;  // this lane's validity word = its 32 rows
-    const int64_t r0 = w * 32;
-    uint32_t okWord = 0;
-    if (r0 < n) {
-      const uint32_t x0 = startCount + static_cast<uint32_t>(r0);
-      uint32_t first = 0, last = static_cast<uint32_t>(numRuns);
-      while (first < last) {
-        const uint32_t mid = first + ((last - first) >> 1);
-        if (counts[mid] > x0) last = mid; else first = mid + 1;
-      }
-      uint32_t run = first ? first - 1 : 0u, next = run + 1 < static_cast<uint32_t>(numRuns) ? counts[run + 1] : 0xFFFFFFFFu;
-      uint32_t v = step == 4 ? reinterpret_cast<const uint32_t *>(values)[run] : step == 2 ? reinterpret_cast<const uint16_t *>(values)[run] : values[run];
-      uint32_t ok = nulls ? get_bit(nulls, run + bitOff) : 1u;
-      for (int j = 0; j < 32; j++) {
-        const uint32_t x = x0 + static_cast<uint32_t>(j);
-        if (x >= next) {
-          while (run + 1 < static_cast<uint32_t>(numRuns) && counts[run + 1] <= x) run++;
-          next = run + 1 < static_cast<uint32_t>(numRuns) ? counts[run + 1] : 0xFFFFFFFFu;
-          v = step == 4 ? reinterpret_cast<const uint32_t *>(values)[run] : step == 2 ? reinterpret_cast<const uint16_t *>(values)[run] : values[run];
-          ok = nulls ? get_bit(nulls, run + bitOff) : 1u;
-        }
-        okWord |= ok << j;
-        tile[33 * lane + j] = v;
-      }
-      if (r0 + 32 > n) okWord &= (1u << static_cast<uint32_t>(n - r0)) - 1u;  // (rows past the end: no bits)
-      outNulls[w] = okWord;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const int64_t base = t * 2048;
-#pragma unroll 4
-    for (int k = 0; k < 32; k++) {
-      const int rr = k * 64 + lane;
-      const int64_t r = base + rr;
-      if (r < n) {
-        const uint32_t v = tile[rr + (rr >> 5)];
-        if (step == 4) reinterpret_cast<uint32_t *>(outValues)[r] = v;
-        else if (step == 2) reinterpret_cast<uint16_t *>(outValues)[r] = static_cast<uint16_t>(v);
-        else outValues[r] = static_cast<uint8_t>(v);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
 // A call's first operand is a run-length encoded column of a 32-bit kind and rows are raw rows (no base counts): the operand
 // is re-bound to the column's decoded copy for the stream's batch — made now, on the call's stream, or found in the batch's
 // cache.  Returns the copy (to be kept alive by whatever is defined over it), or null when the operand stays as it is.
@@ -1183,10 +1169,10 @@ static std::shared_ptr<StreamBuffer> decode_run_length_operand(int device, hipSt
   if (!(a.kind == K_I32 || a.kind == K_U32 || a.kind == K_F32) || a.length == 0) return nullptr;
   DeferLock lock(device);
   auto j = t_state->journals.find(indexVector);  // the batch's rows: what InitIndexVector was called with
-  if (j == t_state->journals.end() || j->second.device != device || j->second.stream != stream || j->second.start != 0 || j->second.n0 <= 0)
+  if (j == t_state->journals.end() || j->second.stream != stream || j->second.start != 0 || j->second.n0 <= 0)
     return nullptr;
   const int rows = j->second.n0;
-  std::vector<RunExpansion> &cache = t_state->expansions[{device, stream}];
+  std::vector<RunExpansion> &cache = t_state->expansions[stream];
   const RunExpansion *hit = nullptr;
   for (const RunExpansion &e : cache)
     if (e.base == a.base && e.nullsOff == a.nullsOff && e.valuesOff == a.valuesOff && e.length == a.length && e.bitOff == a.bitOff &&
@@ -1216,12 +1202,11 @@ static std::shared_ptr<StreamBuffer> decode_run_length_operand(int device, hipSt
 
 // the host writes into (or frees) [r.lo, r.hi): decoded copies of run-length columns that lie in there are no longer what a
 // NEW call would read.  Caller holds the device's DeferLock.
-static void forget_run_expansions(int device, const ByteRange &r) {
+static void forget_run_expansions(const ByteRange &r) {
   for (auto &kv : t_state->expansions) {
-    if (kv.first.first != device) continue;
     auto &v = kv.second;
     for (size_t i = 0; i < v.size();) {
-      const ByteRange src{v[i].base, v[i].base + v[i].valuesOff + static_cast<size_t>(v[i].step) * v[i].length};
+      const ByteRange src = range_of(v[i].base, v[i].valuesOff + static_cast<size_t>(v[i].step) * v[i].length);
       if (src.overlaps(r)) {
         v[i] = v.back();
         v.pop_back();
@@ -1410,11 +1395,7 @@ static int run_transform(const InputVector *ins, int arity, const OutputVector &
   materialize_index_vector(device, indexVector);
   note_sink(device, s, n);
   if (fast) {
-    f.pad = s.type == SINK_MEASURE ? 0 : static_cast<int>(reinterpret_cast<uintptr_t>(s.nulls) & 3);
-    const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
-    const int64_t tiles = (numQuads + kBlock * kTQ - 1) / (kBlock * kTQ);
-    ARES_LAUNCH("transform_fast_kernel", transform_fast_kernel, capped_grid(tiles, 256 * 16), kBlock, stream, f, s, n,
-                numQuads);
+    launch_fast_transform(f, s, n, stream);
   } else if (is_wide(p.a.kind)) {
     const int grid = capped_grid((static_cast<int64_t>(n) + kBlock - 1) / kBlock);
     ARES_LAUNCH("transform_wide_kernel", transform_wide_kernel, grid, kBlock, stream, p, s, n);
@@ -1433,24 +1414,7 @@ static int run_transform(const InputVector *ins, int arity, const OutputVector &
 
 // ---- filters counted in row space (filter_rows_kernel) -----------------------------------------------------------
 namespace {
-// workgroups of `kernel` the device holds at once (occupancy x compute units), per device and kernel, asked once
-int resident_blocks(int device, const void *kernel, int blockSize) {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void *>, int> known;
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = known.find({device, kernel});
-  if (it != known.end()) return it->second;
-  int perCU = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, blockSize, 0) != hipSuccess || perCU < 1) {
-    (void)hipGetLastError();
-    perCU = 4;
-  }
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) {
-    (void)hipGetLastError();
-    cus = 256;
-  }
-  return known[{device, kernel}] = perCU * cus;
-}
+// compute units of the device, asked once
 int compute_units(int device) {
   static std::mutex mu;
   static std::map<int, int> known;
@@ -1463,6 +1427,20 @@ int compute_units(int device) {
     cus = 256;
   }
   return known[device] = cus;
+}
+// workgroups of `kernel` the device holds at once (occupancy x compute units), per device and kernel, asked once
+int resident_blocks(int device, const void *kernel, int blockSize) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void *>, int> known;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = known.find({device, kernel});
+  if (it != known.end()) return it->second;
+  int perCU = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, blockSize, 0) != hipSuccess || perCU < 1) {
+    (void)hipGetLastError();
+    perCU = 4;
+  }
+  return known[{device, kernel}] = perCU * compute_units(device);
 }
 
 // ARES_FILTER_ROWSPACE=0: every filter of the hot shape takes the predicate-vector path (rounds 1-3)
@@ -1483,7 +1461,7 @@ bool row_space_eligible(int device, hipStream_t stream, const uint32_t *indexVec
   if (!fuse_available() || !row_space_enabled()) return false;
   DeferLock lock(device);
   auto j = t_state->journals.find(indexVector);
-  if (j == t_state->journals.end() || !j->second.valid || j->second.device != device || j->second.stream != stream || j->second.start != 0 ||
+  if (j == t_state->journals.end() || !j->second.valid || j->second.stream != stream || j->second.start != 0 ||
       j->second.filters.size() >= static_cast<size_t>(kFusedFilters) || colRows < static_cast<uint32_t>(j->second.n0))
     return false;
   auto c = t_state->compactions.find(indexVector);
@@ -1523,7 +1501,6 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
     }
     if (ins == t_state->compactions.end()) {  // the batch's first filter: the vector is iota(0 .. n)
       PendingCompact fresh{};
-      fresh.device = device;
       fresh.stream = stream;
       fresh.idx = indexVector;
       fresh.virtualIdx = virtualIdx;
@@ -1533,7 +1510,7 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
       ins = t_state->compactions.emplace(indexVector, fresh).first;
     }
     PendingCompact &c = ins->second;
-    FilterHistory &h = t_state->filterHistory[{device, stream}];
+    FilterHistory &h = t_state->filterHistory[stream];
     FilterShape shape{f.akind, f.functor, f.I, f.bkind, f.bbits, f.bok, !c.todo.empty() && same_column(c.todo.back().f, f)};
     const size_t k = h.current.size();
     h.current.push_back(shape);
@@ -1559,8 +1536,7 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
       g.bok = nx.bok;
       two = true;
     }
-    const int64_t numQuads = (static_cast<int64_t>(c.n0) + 3) / 4;
-    const int tiles = static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
+    const int tiles = pred_tiles(c.n0, 0);
     // one wave of workgroups: as many as the device holds at once (a grid of 1.3 x that runs two rounds, the second a
     // third full — measured: 0.104 ms instead of 0.079 per 64 Mi rows), each striding over its share of the tiles
     const bool hasIn = static_cast<bool>(c.bits);
@@ -1646,26 +1622,19 @@ bool prepare_filter(int device, hipStream_t stream, const EvalParams &p, uint32_
 int run_filter_two_phase(int device, hipStream_t stream, FastOperands f, uint32_t *indexVector, uint8_t *pred, int n,
                          RecordID **recordIDVectors, int numForeignTables, bool virtualIdx) {
   f.pad = static_cast<int>(reinterpret_cast<uintptr_t>(pred) & 3);
-  const int64_t numQuads = (static_cast<int64_t>(n) + f.pad + 3) / 4;
-  const int tiles = static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
+  const int tiles = pred_tiles(n, f.pad);
   const int passes = 1 + numForeignTables;
-  // layout: [total, error, tickets[passes], pad][tileCounts][tileOffsets + 1][loaded x passes][one partial count per workgroup]
-  const size_t head = 64;
+  // the workspace's extra words: one partial count per workgroup of the predicate kernel
   constexpr int kPredGridCap = 256 * 16;
   static_assert(kPredGridCap <= kPinnedWords, "the partial counts are read back in one copy");
   const int predGrid = capped_grid(tiles, kPredGridCap);
-  const size_t words = static_cast<size_t>(tiles) * (2 + passes) + 1 + static_cast<size_t>(predGrid);
-  auto wsBuf = std::make_shared<StreamBuffer>(head + 4 * words, stream);
-  uint32_t *w = wsBuf->as<uint32_t>();
-  uint32_t *total = w, *error = w + 1;
-  unsigned int *tickets = w + 2;
-  uint32_t *tileCounts = w + 16, *tileOffsets = tileCounts + tiles, *loaded = tileOffsets + tiles + 1;
-  hip_check(hipMemsetAsync(w, 0, head + 4 * words, stream), "hipMemsetAsync");  // one fill: head, counts, flags
+  auto wsBuf = std::make_shared<StreamBuffer>(CompactSpace::bytes(tiles, passes, predGrid), stream);
+  const CompactSpace cs = clear_compact_space(*wsBuf, tiles, passes, predGrid, stream);
   if (virtualIdx) f.idx = nullptr;  // rows = position
   // lazy: the tile offsets are computed when the compaction runs; with foreign tables they are needed at once
   const bool lazy = numForeignTables == 0 && journal_is_valid(device, indexVector);
-  uint32_t *partials = loaded + static_cast<size_t>(tiles) * passes;
-  ARES_LAUNCH("filter_pred_kernel", filter_pred_kernel, predGrid, kBlock, stream, f, pred, tileCounts, n, tiles,
+  uint32_t *partials = cs.extra();
+  ARES_LAUNCH("filter_pred_kernel", filter_pred_kernel, predGrid, kBlock, stream, f, pred, cs.tileCounts(), n, tiles,
               lazy ? partials : nullptr);
   if (lazy) {
     // The count is known; the compaction waits until somebody needs the compacted vector — a
@@ -1675,49 +1644,22 @@ int run_filter_two_phase(int device, hipStream_t stream, FastOperands f, uint32_
     uint32_t count = 0;
     for (int b = 0; b < predGrid; b++) count += parts[b];
     PendingCompact c;
-    c.device = device;
     c.stream = stream;
     c.idx = indexVector;
     c.pred = pred;
     c.n = n;
     c.pad = f.pad;
-    c.tiles = tiles;
     c.virtualIdx = virtualIdx;
     c.ws = wsBuf;
-    c.ticket = tickets;
-    c.error = error;
-    c.tileOffsets = tileOffsets;
-    c.loaded = loaded;
-    c.tileCounts = tileCounts;
-    c.total = total;
+    c.space = cs;
     DeferLock lock(device);
     t_state->compactions[indexVector] = c;
     return static_cast<int>(count);
   }
-  ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, stream, tileCounts, tileOffsets, tiles, total);
-  const int cgrid = capped_grid((tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
   mem_note_write(device, indexVector, 4ull * static_cast<size_t>(n));
   for (int t = 0; t < numForeignTables; t++) mem_note_write(device, recordIDVectors[t], 8ull * static_cast<size_t>(n));
-  for (int pass = 0; pass < passes; pass++) {
-    CompactWorkspace cw;
-    cw.ticket = tickets + pass;
-    cw.error = error;
-    cw.tileOffsets = tileOffsets;
-    cw.loaded = loaded + static_cast<size_t>(tiles) * pass;
-    if (pass == 0 && virtualIdx)
-      ARES_LAUNCH("filter_compact_kernel<iota>", (filter_compact_kernel<uint32_t, true>), cgrid, kBlock, stream, pred, indexVector,
-                  0u, f.pad, cw, n, tiles);
-    else if (pass == 0)
-      ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, stream, pred, indexVector, 0u,
-                  f.pad, cw, n, tiles);
-    else
-      ARES_LAUNCH("filter_compact_kernel<rid>", (filter_compact_kernel<uint64_t, false>), cgrid, kBlock, stream, pred,
-                  reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), 0u, f.pad, cw, n, tiles);
-  }
-  uint32_t result[2] = {0, 0};  // {survivors, error}
-  read_back_u32(total, result, 2, stream);
-  if (result[1]) throw AlgorithmError("ERROR: filter: compaction wait timed out");
-  return static_cast<int>(result[0]);
+  launch_compaction(cs, pred, indexVector, virtualIdx, recordIDVectors, f.pad, n, stream);
+  return read_compaction_total(cs, stream);
 }
 
 // The generic path — wide operands (arr: an array operand), expressions outside the hot shape and their foreign-table
@@ -1821,10 +1763,6 @@ static int run_filter(const InputVector *ins, int arity, uint32_t *indexVector, 
 // second-stage fusion: notifications from libmem.so, and HashReduce consuming the pending queue
 // ---------------------------------------------------------------------------------------------
 namespace {
-ByteRange range_of(const void *ptr, size_t bytes) {
-  const uint8_t *lo = static_cast<const uint8_t *>(ptr);
-  return ByteRange{lo, lo + (bytes ? bytes : 1)};
-}
 bool touches(const std::vector<ByteRange> &v, const ByteRange &r) {
   for (const ByteRange &x : v)
     if (x.overlaps(r)) return true;
@@ -1834,11 +1772,7 @@ bool touches(const std::vector<ByteRange> &v, const ByteRange &r) {
 bool journal_touched(const uint32_t *indexVector, const FilterJournal &j, const ByteRange &r, bool *indexOnly) {
   const bool idx = range_of(indexVector, 4ull * (j.n0 > 0 ? j.n0 : 1)).overlaps(r);
   bool cols = false;
-  for (size_t k = 0; k < j.filters.size(); k++) {
-    const FastOperands &f = j.filters[k];
-    cols = cols || range_of(f.vals, fast_value_bytes(f, j.colRows[k])).overlaps(r);
-    if (f.nulls) cols = cols || range_of(f.nulls, (static_cast<uint64_t>(j.colRows[k]) + f.bitOff + 7) / 8 + 2).overlaps(r);
-  }
+  for (size_t k = 0; k < j.filters.size(); k++) cols = cols || column_overlaps(j.filters[k], j.colRows[k], r);
   if (indexOnly) *indexOnly = idx && !cols;
   return idx || cols;
 }
@@ -1862,32 +1796,23 @@ void hook_on_wait(int device, void *streamPtr) {
     DeferLock lock(device);
     // a wait on one stream says nothing about the others: their pending work is left alone
     for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();) {
-      if (it->second.device == device && it->second.stream == stream && !it->second.consumed) {
-        launch_init_index(it->first, it->second.start, it->second.n, it->second.stream);
-        it = t_state->iotas.erase(it);
-      } else {
-        ++it;
-      }
+      it = (it->second.stream == stream && !it->second.consumed) ? write_iota(it) : std::next(it);  // (not consumed: no Sort over it)
     }
     for (auto &kv : t_state->pending) {
-      if (kv.first.first != device || kv.first.second != stream || kv.second.jobs.count == 0 || kv.second.overWait) continue;
+      if (kv.first != stream || kv.second.jobs.count == 0 || kv.second.overWait) continue;
       PendingQueue &q = kv.second;
       bool keep = g_fuseEnabled;  // nobody will consume the queue otherwise
       if (keep && q.idx) {  // the survivors must be re-derivable from the filter journal
         auto j = t_state->journals.find(q.idx);
-        keep = j != t_state->journals.end() && j->second.valid && j->second.device == device && j->second.stream == stream &&
-               j->second.start == 0;
+        keep = j != t_state->journals.end() && j->second.valid && j->second.stream == stream && j->second.start == 0;
         if (keep)  // the filters' columns are inputs of the pending work from now on
-          for (size_t k = 0; k < j->second.filters.size(); k++) {
-            const FastOperands &f = j->second.filters[k];
-            q.reads.push_back(range_of(f.vals, fast_value_bytes(f, j->second.colRows[k])));
-            if (f.nulls) q.reads.push_back(range_of(f.nulls, (static_cast<uint64_t>(j->second.colRows[k]) + f.bitOff + 7) / 8 + 2));
-          }
+          for (size_t k = 0; k < j->second.filters.size(); k++)
+            column_ranges(j->second.filters[k], j->second.colRows[k], [&](const ByteRange &c) { q.reads.push_back(c); });
       }
       if (keep)
         q.overWait = true;
       else
-        launch_queue(kv.first.second, q);
+        launch_queue(kv.first, q);
     }
   } catch (std::exception &e) {
     fprintf(stderr, "Exception happened when handling a stream wait: %s\n", e.what());
@@ -1905,7 +1830,7 @@ uintptr_t hook_on_free(int device, void *ptr, size_t bytes) {
     DeviceGuard guard(device);
     DeferLock lock(device);
     for (auto it = t_state->sorts.begin(); it != t_state->sorts.end();) {  // a buffer a lazily defined Sort (+ Reduce) works on goes
-      if (it->second.device == device && sort_touches(it->second, r)) {
+      if (sort_touches(it->second, r)) {
         drop_sort(it->first);
         it = t_state->sorts.begin();
       } else {
@@ -1914,35 +1839,35 @@ uintptr_t hook_on_free(int device, void *ptr, size_t bytes) {
     }
     for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();) {  // an index vector nobody has read yet
       const ByteRange v = range_of(it->first, 4ull * it->second.n);
-      it = (it->second.device == device && v.overlaps(r)) ? t_state->iotas.erase(it) : std::next(it);
+      it = v.overlaps(r) ? t_state->iotas.erase(it) : std::next(it);
     }
-    retire_fills(device, r, true);  // lazy fills of the block die unwritten
-    forget_run_expansions(device, r);
+    retire_fills(r, true);  // lazy fills of the block die unwritten
+    forget_run_expansions(r);
     for (auto it = t_state->journals.begin(); it != t_state->journals.end();) {
       // a journal dies with its index vector or with a column its filters read — unless a queue the
       // host has already waited for still refers to it (then the block is held below, contents intact)
-      const bool dead = it->second.device == device && journal_touched(it->first, it->second, r, nullptr);
+      const bool dead = journal_touched(it->first, it->second, r, nullptr);
       bool kept = false;
       if (dead)
         for (auto &kv : t_state->pending) kept = kept || (kv.second.jobs.count && kv.second.overWait && kv.second.idx == it->first);
       it = (dead && !kept) ? t_state->journals.erase(it) : std::next(it);
     }
     for (auto &kv : t_state->pending) {
-      if (kv.first.first != device || kv.second.jobs.count == 0) continue;
+      if (kv.second.jobs.count == 0) continue;
       if (touches(kv.second.writes, r)) {
-        released.add(kv.first.second);
-        launch_queue(kv.first.second, kv.second);  // an output is freed: run the work, the fence follows it
+        released.add(kv.first);
+        launch_queue(kv.first, kv.second);  // an output is freed: run the work, the fence follows it
       } else if (touches(kv.second.reads, r)) {
         if (kv.second.overWait) {
-          hold = hold_tag(kv.first.second);
+          hold = hold_tag(kv.first);
         } else {  // not even waited for: run it now, the free is fenced behind it
-          released.add(kv.first.second);
-          launch_queue(kv.first.second, kv.second);
+          released.add(kv.first);
+          launch_queue(kv.first, kv.second);
         }
       }
     }
     for (auto it = t_state->compactions.begin(); it != t_state->compactions.end();) {
-      if (it->second.device != device || !compaction_touches(it->second, r)) {
+      if (!compaction_touches(it->second, r)) {
         ++it;
         continue;
       }
@@ -1959,8 +1884,8 @@ uintptr_t hook_on_free(int device, void *ptr, size_t bytes) {
       } else if (queued) {  // transforms the host has not even waited for: run everything now
         for (auto &kv : t_state->pending)
           if (kv.second.jobs.count && kv.second.idx == key) {
-            released.add(kv.first.second);
-            launch_queue(kv.first.second, kv.second);
+            released.add(kv.first);
+            launch_queue(kv.first, kv.second);
           }
         it = t_state->compactions.begin();  // (launch_queue erased the entry)
       } else if (range_of(it->second.idx, 4ull * (it->second.todo.empty() ? it->second.n : it->second.n0)).overlaps(r)) {
@@ -1973,14 +1898,10 @@ uintptr_t hook_on_free(int device, void *ptr, size_t bytes) {
       }
     }
     for (auto it = t_state->limbo.begin(); it != t_state->limbo.end();) {
-      if (it->first.first == device && touches(it->second.writes, r)) {  // the skipped outputs die unseen
-        if (it->second.idx) t_state->compactions.erase(it->second.idx);
-        released.add(it->first.second);
-        const uint32_t *sortIdx = it->second.sortIdx;
-        it = t_state->limbo.erase(it);
-        if (sortIdx) drop_sort(sortIdx);
+      if (touches(it->second.writes, r)) {  // the skipped outputs die unseen
+        it = drop_limbo(it, &released);
       } else {
-        if (it->first.first == device && touches(it->second.reads, r)) hold = hold_tag(it->first.second);
+        if (touches(it->second.reads, r)) hold = hold_tag(it->first);
         ++it;
       }
     }
@@ -2001,30 +1922,25 @@ void hook_on_access(int device, const void *ptr, size_t bytes) {
     DeferLock lock(device);
     for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();) {
       const ByteRange v = range_of(it->first, 4ull * it->second.n);
-      if (it->second.device == device && v.overlaps(r) && it->second.sorted) {
-        t_syncAfterUnlock.push_back(it->second.stream);
-        materialize_sort(it->first);
-        it = t_state->iotas.begin();
-      } else if (it->second.device == device && v.overlaps(r)) {
-        launch_init_index(it->first, it->second.start, it->second.n, it->second.stream);
-        t_syncAfterUnlock.push_back(it->second.stream);
-        it = t_state->iotas.erase(it);
+      if (v.overlaps(r)) {
+        t_syncAfterUnlock.push_back(it->second.stream);  // (the copy may run on another stream)
+        it = write_iota(it);
       } else {
         ++it;
       }
     }
     for (auto &kv : t_state->pending) {
-      if (kv.first.first != device || kv.second.jobs.count == 0) continue;
+      if (kv.second.jobs.count == 0) continue;
       if (touches(kv.second.writes, r) || touches(kv.second.reads, r)) {
-        released.add(kv.first.second);
-        launch_queue(kv.first.second, kv.second);
+        released.add(kv.first);
+        launch_queue(kv.first, kv.second);
       }
     }
-    forget_run_expansions(device, r);  // (a copy INTO a run-length column: later calls decode it again)
-    materialize_fills(device, &r, &t_syncAfterUnlock);  // (the copy may run on another stream: wait for the fill)
-    materialize_limbo(device, &r, &released);
+    forget_run_expansions(r);  // (a copy INTO a run-length column: later calls decode it again)
+    materialize_fills(&r, &t_syncAfterUnlock);  // (the copy may run on another stream: wait for the fill)
+    materialize_limbo(&r, &released);
     for (auto it = t_state->compactions.begin(); it != t_state->compactions.end();) {
-      if (it->second.device == device && compaction_touches(it->second, r)) {
+      if (compaction_touches(it->second, r)) {
         const hipStream_t cs = it->second.stream;
         run_compaction(it->first);
         t_syncAfterUnlock.push_back(cs);
@@ -2036,7 +1952,7 @@ void hook_on_access(int device, const void *ptr, size_t bytes) {
     // a copy into an index vector or into a column a journalled filter has read: the survivors can
     // no longer be re-derived (queues that depended on the journal were launched above)
     for (auto it = t_state->journals.begin(); it != t_state->journals.end();)
-      it = (it->second.device == device && journal_touched(it->first, it->second, r, nullptr)) ? t_state->journals.erase(it) : std::next(it);
+      it = journal_touched(it->first, it->second, r, nullptr) ? t_state->journals.erase(it) : std::next(it);
   } catch (std::exception &e) {
     fprintf(stderr, "Exception happened when handling a device copy: %s\n", e.what());
   }
@@ -2065,43 +1981,32 @@ void hook_on_stream_destroy(int device, void *streamPtr) {
     {
       DeferLock lock(device);
       for (auto it = t_state->sorts.begin(); it != t_state->sorts.end();) {
-        if (it->second.device == device && it->second.stream == stream) {
+        if (it->second.stream == stream) {
           drop_sort(it->first);
           it = t_state->sorts.begin();
         } else {
           ++it;
         }
       }
-      t_state->pending.erase({device, stream});
-      t_state->expansions.erase({device, stream});
-      auto lim = t_state->limbo.find({device, stream});
-      if (lim != t_state->limbo.end()) {
-        if (lim->second.idx) t_state->compactions.erase(lim->second.idx);
-        t_state->limbo.erase(lim);
-      }
+      t_state->pending.erase(stream);
+      t_state->expansions.erase(stream);
+      auto lim = t_state->limbo.find(stream);
+      if (lim != t_state->limbo.end()) drop_limbo(lim, nullptr);  // (the stream's tag is released below, whatever was held under it)
       for (auto it = t_state->journals.begin(); it != t_state->journals.end();)
-        it = (it->second.device == device && it->second.stream == stream) ? t_state->journals.erase(it) : std::next(it);
+        it = it->second.stream == stream ? t_state->journals.erase(it) : std::next(it);
       for (auto it = t_state->compactions.begin(); it != t_state->compactions.end();)
-        it = (it->second.device == device && it->second.stream == stream) ? t_state->compactions.erase(it) : std::next(it);
+        it = it->second.stream == stream ? t_state->compactions.erase(it) : std::next(it);
       for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();)
-        it = (it->second.device == device && it->second.stream == stream) ? t_state->iotas.erase(it) : std::next(it);
-      t_state->filterHistory.erase({device, stream});
+        it = it->second.stream == stream ? t_state->iotas.erase(it) : std::next(it);
+      t_state->filterHistory.erase(stream);
       // lazy fills that were defined on this stream and are still unwritten: from now on they are written on the stream
       // of whoever needs them (the null stream stands for "the caller's", see launch_fill)
       for (auto &kv : t_state->fills)
-        if (kv.second.device == device && kv.second.stream == stream) kv.second.streamGone = true;
+        if (kv.second.stream == stream) kv.second.streamGone = true;
       // error words of this stream's lazy compactions: the stream is idle, their copies have landed; the events go now
       for (size_t i = 0; i < t_state->errorChecks.size();) {
-        ErrorCheck &c = t_state->errorChecks[i];
-        if (c.device == device && c.stream == stream) {
-          t_state->errorSeen = t_state->errorSeen || *c.pinned != 0;
-          (void)hipEventDestroy(c.done);
-          t_state->errorSlots.push_back(c.pinned);
-          t_state->errorChecks[i] = std::move(t_state->errorChecks.back());
-          t_state->errorChecks.pop_back();
-        } else {
-          i++;
-        }
+        if (t_state->errorChecks[i].stream == stream) t_state->errorSeen = retire_error_check(i) || t_state->errorSeen;
+        else i++;
       }
     }
     profiler_stream_gone(stream);
@@ -2125,11 +2030,11 @@ void launch_pending_writers(int device, const void *ptr, size_t bytes) {
   {
     DeferLock lock(device);
     for (auto &kv : t_state->pending) {
-      if (kv.first.first != device || kv.second.jobs.count == 0 || !touches(kv.second.writes, r)) continue;
-      if (kv.second.overWait) released.add(kv.first.second);
-      launch_queue(kv.first.second, kv.second);
+      if (kv.second.jobs.count == 0 || !touches(kv.second.writes, r)) continue;
+      if (kv.second.overWait) released.add(kv.first);
+      launch_queue(kv.first, kv.second);
     }
-    materialize_limbo(device, &r, &released);
+    materialize_limbo(&r, &released);
   }
   released.run(device);
 }
@@ -2171,12 +2076,12 @@ bool measure_job_matches(const SinkD &s, const uint8_t *measureRows, int valueBy
 }
 // survivors of the queue's rows: the whole batch (no filter ran: no journal, n0 = pq.n) or what the journalled filters keep
 // (n0 = the rows they read).  false: filters ran and the survivors cannot be re-derived.  Caller holds the device's DeferLock.
-bool queue_survivors(int device, const PendingQueue &pq, const FilterJournal **journal, int *n0) {
+bool queue_survivors(const PendingQueue &pq, const FilterJournal **journal, int *n0) {
   *journal = nullptr;
   *n0 = pq.n;
   if (!pq.idx) return true;
   auto j = t_state->journals.find(pq.idx);
-  if (j == t_state->journals.end() || !j->second.valid || j->second.start != 0 || j->second.device != device) return false;
+  if (j == t_state->journals.end() || !j->second.valid || j->second.start != 0) return false;
   *journal = &j->second;
   *n0 = j->second.n0;
   return true;
@@ -2213,6 +2118,16 @@ void take_queue(PendingQueue &pq, PendingQueue &q) {
     t_state->journals.erase(q.idx);
   }
 }
+// *a: the aggregate of the call, when there is such an aggregate and the fused consumer asked (`supported`) takes it
+template <typename Supported>
+bool supported_agg_spec(int aggFunc, int valueBytes, Supported &&supported, AggSpec *a) {
+  try {
+    *a = make_agg_spec(aggFunc, valueBytes);
+    return supported(*a);
+  } catch (std::exception &) {
+    return false;
+  }
+}
 // Runs a fused attempt.  An exception it throws still means "declined" (-1: the caller runs the ordinary sequence), but what
 // it said is kept: a line in the ARES_RTC_TRACE file and, with ARES_HR_TRACE, on stderr.
 template <typename Attempt>
@@ -2244,7 +2159,7 @@ bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const Dimensi
   AggSpec a;
   {
     DeferLock lock(device);
-    auto it = t_state->pending.find({device, stream});
+    auto it = t_state->pending.find(stream);
     if (it == t_state->pending.end() || it->second.jobs.count == 0) return false;
     PendingQueue &pq = it->second;
     bool ok = !forcedGlobal;
@@ -2261,16 +2176,9 @@ bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const Dimensi
     int dimJob[kFusedDims], measureJob = -1;
     ok = ok && prev >= 0 && pq.n > 0 && match_jobs(pq, in, L, prev, dimJob, &measureJob) && measureJob >= 0 &&
          measure_job_matches(pq.jobs.s[measureJob], inValues + static_cast<size_t>(valueBytes) * prev, valueBytes, aggFunc);
-    if (ok) {
-      try {
-        a = make_agg_spec(aggFunc, valueBytes);
-        ok = hash_reduce_lds_supported(a);
-      } catch (std::exception &) {
-        ok = false;
-      }
-    }
+    ok = ok && supported_agg_spec(aggFunc, valueBytes, hash_reduce_lds_supported, &a);
     const FilterJournal *journal = nullptr;
-    ok = ok && queue_survivors(device, pq, &journal, &n0) && columns_cover(pq.colRows, pq.jobs.count, n0) &&
+    ok = ok && queue_survivors(pq, &journal, &n0) && columns_cover(pq.colRows, pq.jobs.count, n0) &&
          plan_from_queue(plan, pq, L, dimJob, measureJob, valueBytes, 0, 0, journal, n0);
     // the precompiled generic scan holds nd + 2 column slots; a narrow plan only ever runs on generated kernels (kFusedCols)
     ok = ok && (plan.numCols <= nd + 2 || fused_plan_narrow(plan, nd));
@@ -2290,7 +2198,7 @@ bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const Dimensi
     g_releaseHeld(device, hold_tag(stream));
     return false;
   }
-  t_state->limbo[{device, stream}] = q;  // launchable until the next batch begins (begin_batch)
+  t_state->limbo[stream] = q;  // launchable until the next batch begins (begin_batch)
   *groups = result;
   return true;
 }
@@ -2303,10 +2211,29 @@ bool same_vector(const DimensionVector &a, const DimensionVector &b) {
 }
 }  // namespace
 
+// caller holds the device's DeferLock: [at, at + bytes) is from now on what the lazily defined Sort (+ Reduce) `ps` would
+// write there — lazy fills under it retire, a marker among the fills takes their place
+static void mark_sort_output(const PendingSort &ps, void *at, size_t bytes, int unit) {
+  uint8_t *p = static_cast<uint8_t *>(at);
+  retire_fills(range_of(p, bytes), false);
+  t_state->fills[p] = PendingFill{ps.stream, bytes, 0, unit, false, ps.keys.IndexVector};
+}
+// caller holds the device's DeferLock: Sort(ps.keys, ps.length) is defined, not run — the hash vector becomes a marker, the
+// index vector's iota entry `io` "what Sort leaves" (nobody takes it for an iota any more, only its own readers write it)
+// (`io` lives in t_state->iotas, and retire_fills below may run drop_sort / materialize_sort over OTHER definitions: they erase
+// an iota entry only where it is `sorted` and its own sort is entered — `io` is neither until the lines after the call, so the
+// reference holds.  The flags are therefore set last.)
+static void define_sort(const PendingSort &ps, PendingIota &io) {
+  mark_sort_output(ps, ps.keys.HashValues, 8ull * static_cast<size_t>(ps.length), 8);
+  t_state->sorts[ps.keys.IndexVector] = ps;
+  io.consumed = true;
+  io.sorted = true;
+}
+
 // caller holds the device's DeferLock.  A lazily defined Sort has been consumed by a Reduce whose kernels wrote `result` groups:
 // the hash vector, the input's index vector and the output's index vector stay DEFINED (what Sort and Reduce would have left
 // there); whoever reads them replays the sequence (materialize_sort)
-static void enter_reduced_sort(int device, hipStream_t stream, PendingSort ps, const DimensionVector &in, uint8_t *inValues,
+static void enter_reduced_sort(hipStream_t stream, PendingSort ps, const DimensionVector &in, uint8_t *inValues,
                                const DimensionVector &out, uint8_t *outValues, int valueBytes, int length, int aggFunc, int result) {
   ps.reduced = true;
   ps.outKeys = out;
@@ -2315,23 +2242,9 @@ static void enter_reduced_sort(int device, hipStream_t stream, PendingSort ps, c
   ps.valueBytes = valueBytes;
   ps.aggFunc = aggFunc;
   ps.groups = result;
-  t_state->sorts[in.IndexVector] = ps;
-  PendingIota io{device, stream, 0, length};
-  io.consumed = true;
-  io.sorted = true;
-  t_state->iotas[in.IndexVector] = io;
-  uint8_t *hv = reinterpret_cast<uint8_t *>(in.HashValues);
-  retire_fills(device, ByteRange{hv, hv + 8ull * static_cast<size_t>(length)}, false);
-  PendingFill marker{device, stream, 8ull * static_cast<size_t>(length), 0, 8, false};
-  marker.sortIdx = in.IndexVector;
-  t_state->fills[hv] = marker;
-  if (result > 0) {
-    uint8_t *oi = reinterpret_cast<uint8_t *>(out.IndexVector);
-    retire_fills(device, ByteRange{oi, oi + 4ull * static_cast<size_t>(result)}, false);
-    PendingFill om{device, stream, 4ull * static_cast<size_t>(result), 0, 4, false};
-    om.sortIdx = in.IndexVector;
-    t_state->fills[oi] = om;
-  }
+  // (ps is the definition this Reduce consumed: ps.keys is `in`, ps.length is `length`, ps.stream is `stream`)
+  define_sort(ps, t_state->iotas[in.IndexVector] = PendingIota{stream, 0, length});
+  if (result > 0) mark_sort_output(ps, out.IndexVector, 4ull * static_cast<size_t>(result), 4);
 }
 
 // Sort(keys, length) when the rows [length - n, length) of `keys` are what this stream's pending transforms would write and
@@ -2349,31 +2262,21 @@ bool define_lazy_sort(int device, hipStream_t stream, const DimensionVector &key
     return false;
   }
   DeferLock lock(device);
-  auto io = t_state->iotas.find(keys.IndexVector);
-  if (io == t_state->iotas.end() || io->second.device != device || io->second.start != 0 || io->second.n != length || io->second.consumed ||
-      io->second.sorted)
-    return false;
-  auto it = t_state->pending.find({device, stream});
+  PendingIota *io = lazy_iota(keys.IndexVector, length);
+  if (!io || io->consumed) return false;
+  auto it = t_state->pending.find(stream);
   if (it == t_state->pending.end() || it->second.jobs.count == 0) return false;
   const PendingQueue &pq = it->second;
   const int prev = length - pq.n;
   int dimJob[kFusedDims], measureJob = -1, n0 = 0;
   const FilterJournal *journal = nullptr;
   if (pq.n <= 0 || prev < 0 || !match_jobs(pq, keys, L, prev, dimJob, &measureJob)) return false;
-  if (!queue_survivors(device, pq, &journal, &n0)) return false;  // the survivors must be re-derivable from the filter journal
-  uint8_t *hv = reinterpret_cast<uint8_t *>(keys.HashValues);
-  retire_fills(device, ByteRange{hv, hv + 8ull * static_cast<size_t>(length)}, false);
+  if (!queue_survivors(pq, &journal, &n0)) return false;  // the survivors must be re-derivable from the filter journal
   PendingSort ps{};
-  ps.device = device;
   ps.stream = stream;
   ps.keys = keys;
   ps.length = length;
-  t_state->sorts[keys.IndexVector] = ps;
-  io->second.consumed = true;
-  io->second.sorted = true;
-  PendingFill marker{device, stream, 8ull * static_cast<size_t>(length), 0, 8, false};
-  marker.sortIdx = keys.IndexVector;
-  t_state->fills[hv] = marker;
+  define_sort(ps, *io);
   return true;
 }
 
@@ -2399,13 +2302,13 @@ bool lazy_vector_sort_candidate(int device, const DimensionVector &keys, int len
       !keys.IndexVector || keys.VectorCapacity < length || !vector_sort_layout(keys))
     return false;
   DeferLock lock(device);
-  auto io = t_state->iotas.find(keys.IndexVector);
-  if (io == t_state->iotas.end() || io->second.device != device || io->second.start != 0 || io->second.n != length || io->second.consumed ||
-      io->second.sorted) {
-    if (trace) fprintf(stderr, "lazy_vector_sort_candidate: index vector is %s\n", io == t_state->iotas.end() ? "not a lazy iota" : "a lazy iota of another kind");
+  PendingIota *io = lazy_iota(keys.IndexVector, length);
+  if (!io || io->consumed) {
+    if (trace)
+      fprintf(stderr, "lazy_vector_sort_candidate: index vector is %s\n", t_state->iotas.count(keys.IndexVector) ? "a lazy iota of another kind" : "not a lazy iota");
     return false;
   }
-  io->second.consumed = true;
+  io->consumed = true;
   return true;
 }
 
@@ -2414,22 +2317,14 @@ bool lazy_vector_sort_candidate(int device, const DimensionVector &keys, int len
 bool define_lazy_sort_vectors(int device, hipStream_t stream, const DimensionVector &keys, int length) {
   {
     DeferLock lock(device);
-    auto io = t_state->iotas.find(keys.IndexVector);
-    if (io != t_state->iotas.end() && io->second.device == device && io->second.start == 0 && io->second.n == length && io->second.consumed &&
-        !io->second.sorted) {
-      uint8_t *hv = reinterpret_cast<uint8_t *>(keys.HashValues);
-      retire_fills(device, ByteRange{hv, hv + 8ull * static_cast<size_t>(length)}, false);
+    PendingIota *io = lazy_iota(keys.IndexVector, length);
+    if (io && io->consumed) {  // (lazy_vector_sort_candidate marked it)
       PendingSort ps{};
-      ps.device = device;
       ps.stream = stream;
       ps.keys = keys;
       ps.length = length;
       ps.fromVectors = true;
-      t_state->sorts[keys.IndexVector] = ps;
-      io->second.sorted = true;
-      PendingFill marker{device, stream, 8ull * static_cast<size_t>(length), 0, 8, false};
-      marker.sortIdx = keys.IndexVector;
-      t_state->fills[hv] = marker;
+      define_sort(ps, *io);
       return true;
     }
   }
@@ -2463,8 +2358,8 @@ static bool reduced_sort_done(int device, hipStream_t stream, const PendingSort 
   mem_note_dim_rows(device, out, 0, static_cast<size_t>(result));
   mem_note_write(device, outValues, static_cast<size_t>(valueBytes) * static_cast<size_t>(result));
   DeferLock lock(device);
-  if (consumed) t_state->limbo[{device, stream}] = *consumed;
-  enter_reduced_sort(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result);
+  if (consumed) t_state->limbo[stream] = *consumed;
+  enter_reduced_sort(stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result);
   *groups = result;
   return true;
 }
@@ -2488,17 +2383,10 @@ static bool reduce_lazy_vector_sort(int device, hipStream_t stream, const Dimens
     auto st = t_state->sorts.find(in.IndexVector);
     if (st == t_state->sorts.end()) return false;
     ps = st->second;
-    bool ok = !ps.reduced && ps.fromVectors && ps.device == device && ps.stream == stream && ps.length == length && same_vector(ps.keys, in) &&
+    bool ok = !ps.reduced && ps.fromVectors && ps.stream == stream && ps.length == length && same_vector(ps.keys, in) &&
               inValues && out.DimValues && out.IndexVector && outValues && out.VectorCapacity >= length && in.VectorCapacity >= length &&
               memcmp(out.NumDimsPerDimWidth, in.NumDimsPerDimWidth, sizeof(in.NumDimsPerDimWidth)) == 0 && (valueBytes == 4 || valueBytes == 8);
-    if (ok) {
-      try {
-        a = make_agg_spec(aggFunc, valueBytes);
-        ok = fused_sort_reduce_supported(a);
-      } catch (std::exception &) {
-        ok = false;
-      }
-    }
+    ok = ok && supported_agg_spec(aggFunc, valueBytes, fused_sort_reduce_supported, &a);
     if (!ok) {
       materialize_sort(in.IndexVector);
       return false;
@@ -2539,30 +2427,23 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
     auto st = t_state->sorts.find(in.IndexVector);
     if (st == t_state->sorts.end()) return false;  // nothing lazy about this Sort
     ps = st->second;
-    bool ok = !ps.reduced && ps.device == device && ps.stream == stream && ps.length == length && same_vector(ps.keys, in) && inValues &&
+    bool ok = !ps.reduced && ps.stream == stream && ps.length == length && same_vector(ps.keys, in) && inValues &&
               out.DimValues && out.IndexVector && outValues && out.VectorCapacity >= length &&
               memcmp(out.NumDimsPerDimWidth, in.NumDimsPerDimWidth, sizeof(in.NumDimsPerDimWidth)) == 0;
     DimLayoutD L;
     memset(&L, 0, sizeof(L));
     if (ok) L = make_dim_layout(in.NumDimsPerDimWidth);
     nd = L.numDims;
-    auto it = t_state->pending.find({device, stream});
+    auto it = t_state->pending.find(stream);
     ok = ok && it != t_state->pending.end() && it->second.jobs.count > 0;
     int dimJob[kFusedDims], measureJob = -1;
     if (ok) {
       prev = length - it->second.n;
       ok = it->second.n > 0 && prev >= 0 && match_jobs(it->second, in, L, prev, dimJob, &measureJob);
     }
-    if (ok) {
-      try {
-        a = make_agg_spec(aggFunc, valueBytes);
-        ok = fused_sort_reduce_supported(a);
-      } catch (std::exception &) {
-        ok = false;
-      }
-    }
+    ok = ok && supported_agg_spec(aggFunc, valueBytes, fused_sort_reduce_supported, &a);
     const FilterJournal *journal = nullptr;
-    ok = ok && queue_survivors(device, it->second, &journal, &n0) && columns_cover(it->second.colRows, it->second.jobs.count, n0);
+    ok = ok && queue_survivors(it->second, &journal, &n0) && columns_cover(it->second.colRows, it->second.jobs.count, n0);
     if (ok) {
       const PendingQueue &pq = it->second;
       uint8_t *measureRows = inValues + static_cast<size_t>(valueBytes) * prev;
@@ -2570,7 +2451,7 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
         ok = measure_job_matches(pq.jobs.s[measureJob], measureRows, valueBytes, aggFunc);
       } else {  // a constant measure (COUNT(*)): the rows are a lazy fill
         auto f = t_state->fills.find(measureRows);
-        ok = f != t_state->fills.end() && f->second.device == device && !f->second.sortIdx && f->second.unit == valueBytes &&
+        ok = f != t_state->fills.end() && !f->second.sortIdx && f->second.unit == valueBytes &&
              f->second.bytes == static_cast<size_t>(valueBytes) * pq.n;
         if (ok) {
           constMeasure = true;
@@ -2620,32 +2501,6 @@ bool fuse_pending_into_sort_reduce(int device, hipStream_t stream, const Dimensi
   return reduced_sort_done(device, stream, ps, in, inValues, out, outValues, valueBytes, length, aggFunc, result, &q, groups);
 }
 
-// tile counts of an existing predicate vector, in filter_pred_kernel's tile geometry
-__global__ __launch_bounds__(kBlock) void pred_count_kernel(const uint8_t *pred, uint32_t *tileCounts, int pad, int n,
-                                                            int numTiles) {
-  const int lane = threadIdx.x & 63;
-  for (int tile = blockIdx.x; tile < numTiles; tile += gridDim.x) {
-    const int64_t tq = static_cast<int64_t>(tile) * (kBlock * kPQ);
-    uint32_t count = 0;
-#pragma unroll
-    for (int q = 0; q < kPQ; q++) {
-      const int64_t i0 = (tq + threadIdx.x + static_cast<int64_t>(q) * kBlock) * 4 - pad;
-      if (i0 >= 0 && i0 + 3 < n) {
-        const uint32_t pb = *reinterpret_cast<const uint32_t *>(pred + i0);
-        count += ((pb & 0xFFu) ? 1u : 0u) + ((pb & 0xFF00u) ? 1u : 0u) + ((pb & 0xFF0000u) ? 1u : 0u) +
-                 ((pb & 0xFF000000u) ? 1u : 0u);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-          if (i0 + j >= 0 && i0 + j < n && pred[i0 + j]) count++;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) count += __shfl_xor(count, off);
-    if (lane == 0 && count) atomicAdd(tileCounts + tile, count);
-  }
-}
-
 // Stable in-place compaction of the index vector and of every RecordID vector by an existing
 // predicate vector (keep = byte != 0): the tail of the two-phase filter, for callers that compute
 // their predicate elsewhere (geo intersection).
@@ -2658,37 +2513,13 @@ int compact_by_predicate(const uint8_t *pred, uint32_t *indexVector, RecordID **
     for (int t = 0; t < numForeignTables; t++) mem_note_write(device, recordIDVectors[t], 8ull * static_cast<size_t>(n));
   }
   const int pad = static_cast<int>(reinterpret_cast<uintptr_t>(pred) & 3);
-  const int64_t numQuads = (static_cast<int64_t>(n) + pad + 3) / 4;
-  const int tiles = static_cast<int>((numQuads + kBlock * kPQ - 1) / (kBlock * kPQ));
+  const int tiles = pred_tiles(n, pad);
   const int passes = 1 + numForeignTables;
-  const size_t head = 64;
-  const size_t words = static_cast<size_t>(tiles) * (2 + passes) + 1;
-  StreamBuffer wsBuf(head + 4 * words, stream);
-  uint32_t *w = wsBuf.as<uint32_t>();
-  uint32_t *total = w, *error = w + 1;
-  unsigned int *tickets = w + 2;
-  uint32_t *tileCounts = w + 16, *tileOffsets = tileCounts + tiles, *loaded = tileOffsets + tiles + 1;
-  hip_check(hipMemsetAsync(w, 0, head + 4 * words, stream), "hipMemsetAsync");
-  ARES_LAUNCH("pred_count_kernel", pred_count_kernel, capped_grid(tiles, 256 * 16), kBlock, stream, pred, tileCounts, pad, n, tiles);
-  ARES_LAUNCH("filter_scan_kernel", filter_scan_kernel, 1, 1024, stream, tileCounts, tileOffsets, tiles, total);
-  const int cgrid = capped_grid((tiles + kTilesPerTicket - 1) / kTilesPerTicket, 256 * 8);
-  for (int pass = 0; pass < passes; pass++) {
-    CompactWorkspace cw;
-    cw.ticket = tickets + pass;
-    cw.error = error;
-    cw.tileOffsets = tileOffsets;
-    cw.loaded = loaded + static_cast<size_t>(tiles) * pass;
-    if (pass == 0)
-      ARES_LAUNCH("filter_compact_kernel", (filter_compact_kernel<uint32_t, false>), cgrid, kBlock, stream, pred, indexVector, 0u,
-                  pad, cw, n, tiles);
-    else
-      ARES_LAUNCH("filter_compact_kernel<rid>", (filter_compact_kernel<uint64_t, false>), cgrid, kBlock, stream, pred,
-                  reinterpret_cast<uint64_t *>(recordIDVectors[pass - 1]), 0u, pad, cw, n, tiles);
-  }
-  uint32_t result[2] = {0, 0};  // {survivors, error}
-  read_back_u32(total, result, 2, stream);
-  if (result[1]) throw AlgorithmError("ERROR: filter: compaction wait timed out");
-  return static_cast<int>(result[0]);
+  StreamBuffer wsBuf(CompactSpace::bytes(tiles, passes, 0), stream);
+  const CompactSpace cs = clear_compact_space(wsBuf, tiles, passes, 0, stream);
+  ARES_LAUNCH("pred_count_kernel", pred_count_kernel, capped_grid(tiles, 256 * 16), kBlock, stream, pred, cs.tileCounts(), pad, n, tiles);
+  launch_compaction(cs, pred, indexVector, false, recordIDVectors, pad, n, stream);
+  return read_compaction_total(cs, stream);
 }
 
 }  // namespace ares
@@ -2701,7 +2532,7 @@ size_t AresStreamEvents(int device, void *stream) {
   size_t n = profiler_stream_events(reinterpret_cast<hipStream_t>(stream));
   if (device < 0 || device >= kMaxDevices) return n;
   DeferLock lock(device);
-  for (const ErrorCheck &c : t_state->errorChecks) n += c.device == device && c.stream == reinterpret_cast<hipStream_t>(stream);
+  for (const ErrorCheck &c : t_state->errorChecks) n += c.stream == reinterpret_cast<hipStream_t>(stream);
   return n;
 }
 
