@@ -305,6 +305,14 @@ class Backend:
         self._algo.AresSelectStats(c)
         return {"batches": int(c[0]), "declined": int(c[1]), "tiles": int(c[2]), "rows": int(c[3])}
 
+    def select_run_stats(self):
+        """{rejected, staged}: tiles of AresFusedFilterSelect thrown away by one run of a run-length filter column, and tiles
+        that staged run ends in LDS, since the process started."""
+        c = (C.c_ulonglong * 2)()
+        self._algo.AresSelectRunStats.argtypes, self._algo.AresSelectRunStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresSelectRunStats(c)
+        return {"rejected": int(c[0]), "staged": int(c[1])}
+
     def profiler_enable(self, on=True):
         self._algo.AresProfilerEnable(1 if on else 0)
 

@@ -11,6 +11,14 @@
 // the grid is scanned whatever the batch size.  Values and validity bytes come from the functions the transform kernels
 // use (eval_quad, compare_tile, cvt32), so the bytes written equal the per-node sequence's for the same rows.
 //
+// Run-length (mode 3) columns — the sort columns of archive batches — are read where they lie (select_scan_kernel<true>): per
+// tile and column two scalar binary searches over the counts give the runs of the tile's first and last row.  One run: value
+// and validity are a broadcast, and a filter whose run is null or fails the comparison REJECTS the tile — its look-back word is
+// published with count 0 and no other column is read.  Several runs: the run ends inside the tile (at most 4095) are staged
+// in LDS, a lane searches them once per quad and walks the quad's other rows along them.  Plans without such a column run
+// select_scan_kernel<false>, the instruction sequence of before.  A GeoPoint column in the run-length layout is declined: the
+// per-node sequence never decodes it (binding.hpp) and reads its rows past the run arrays.
+//
 // Stores go straight to the slots: the survivors of a wavefront's quads have consecutive ranks, so each store instruction
 // of a wavefront covers one contiguous byte range, and a quad that survives whole is stored as one 16 / 8 / 4 byte access.
 #include "select_scan.hpp"
@@ -105,6 +113,145 @@ __device__ __forceinline__ void load_column_tile(const FastOperands &f, int64_t 
   }
 }
 
+// ---- run-length (mode 3) columns ------------------------------------------------------------------------------------
+// Runs of rows x0 <= x1 as locate() (device_model.hpp) finds them: the number of counts[0 .. runs) at or below the row, less
+// one — rows past the last count take the last run, and counts[runs] is never read.  Both searches advance together; with
+// scalar arguments they are scalar loads.
+struct RunSpan {
+  uint32_t lo, hi;
+};
+__device__ __forceinline__ RunSpan locate_span(const uint32_t *counts, uint32_t runs, uint32_t x0, uint32_t x1) {
+  uint32_t f0 = 0, l0 = runs, f1 = 0, l1 = runs;
+  while (f0 < l0 || f1 < l1) {
+    const uint32_t m0 = min(f0 + ((l0 - f0) >> 1), runs - 1), m1 = min(f1 + ((l1 - f1) >> 1), runs - 1);
+    const uint32_t c0 = counts[m0], c1 = counts[m1];
+    if (f0 < l0) {
+      if (c0 > x0) l0 = m0; else f0 = m0 + 1;
+    }
+    if (f1 < l1) {
+      if (c1 > x1) l1 = m1; else f1 = m1 + 1;
+    }
+  }
+  RunSpan s;
+  s.lo = f0 ? f0 - 1 : 0u;
+  s.hi = f1 ? f1 - 1 : 0u;
+  return s;
+}
+
+// value of run `run`, widened as load_column_tile widens a row's, and its validity bit
+__device__ __forceinline__ uint32_t run_value(const FastOperands &f, uint32_t run) {
+  if (f.step == 2) {
+    const uint32_t raw = reinterpret_cast<const uint16_t *>(f.vals)[run];
+    return f.akind == K_I32 ? static_cast<uint32_t>(static_cast<int32_t>(static_cast<int16_t>(raw))) : raw;
+  }
+  if (f.step == 1) {
+    const uint32_t raw = reinterpret_cast<const uint8_t *>(f.vals)[run];
+    return f.akind == K_I32 ? static_cast<uint32_t>(static_cast<int32_t>(static_cast<int8_t>(raw))) : raw;
+  }
+  return f.vals[run];
+}
+__device__ __forceinline__ uint32_t run_valid(const FastOperands &f, uint32_t run) {
+  const uint32_t bit = run + f.bitOff;
+  return (static_cast<uint32_t>(f.nulls[bit >> 3]) >> (bit & 7u)) & 1u;
+}
+
+// The runs of one column inside one tile.  span.lo == span.hi: one run.  Otherwise ends[i] (i < m = hi - lo) is the end of
+// run lo + i relative to the tile's first row, in (0, 4095]: staged in LDS, or — m beyond the tile's rows, which takes runs
+// of no rows — read from the counts.
+struct TileRuns {
+  RunSpan span;
+  uint32_t m;
+  bool inLds;
+  const uint32_t *lds;     // the staged ends
+  const uint32_t *counts;  // counts + lo + 1
+  uint32_t row0;
+  __device__ __forceinline__ uint32_t end(uint32_t i) const { return inLds ? lds[i] : counts[i] - row0; }
+};
+
+// (every thread of the workgroup, uniformly)
+__device__ __forceinline__ TileRuns tile_runs(const uint32_t *counts, uint32_t runs, uint32_t row0, uint32_t lastRow, uint32_t *sEnds, bool &staged) {
+  TileRuns t;
+  t.span = locate_span(counts, runs, row0, lastRow);
+  t.m = t.span.hi - t.span.lo;
+  t.counts = counts + t.span.lo + 1;
+  t.row0 = row0;
+  t.lds = sEnds;
+  t.inLds = false;
+  if (t.m > 0 && t.m < static_cast<uint32_t>(kSelectTile)) {
+    __syncthreads();  // (the searches of the column staged before are over)
+    for (uint32_t i = threadIdx.x; i < t.m; i += kSelectBlock) sEnds[i] = t.counts[i] - row0;
+    __syncthreads();
+    t.inLds = true;
+    staged = true;
+  }
+  return t;
+}
+
+// runs of the four rows of the quad whose first row is `rel` rows into the tile: one search, then a walk along the ends
+__device__ __forceinline__ void quad_runs(const TileRuns &t, uint32_t rel, uint32_t (&run)[4]) {
+  uint32_t first = 0, last = t.m;
+  while (first < last) {
+    const uint32_t mid = first + ((last - first) >> 1);
+    if (t.end(mid) > rel) last = mid; else first = mid + 1;
+  }
+  run[0] = t.span.lo + first;
+#pragma unroll
+  for (uint32_t j = 1; j < 4; j++) {
+    while (first < t.m && t.end(first) <= rel + j) first++;
+    run[j] = t.span.lo + first;
+  }
+}
+
+__device__ __forceinline__ void load_runs_tile(const FastOperands &f, const TileRuns &t, uint32_t (&vals)[Q][4], uint32_t (&okb)[Q]) {
+  if (t.m == 0) {  // one run: a broadcast
+    const uint32_t v = run_value(f, t.span.lo), ok = run_valid(f, t.span.lo) ? 0xFu : 0u;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) vals[q][j] = v;
+      okb[q] = ok;
+    }
+    return;
+  }
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    uint32_t run[4];
+    quad_runs(t, (static_cast<uint32_t>(q) * kSelectBlock + threadIdx.x) * 4u, run);
+    okb[q] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      vals[q][j] = run_value(f, run[j]);
+      okb[q] |= run_valid(f, run[j]) << j;
+    }
+  }
+}
+
+// store_wide_dim for a mode-3 column: the surviving rows' RUNS' stored bytes and validity bits
+__device__ __forceinline__ void store_wide_runs(const SelectDimD &D, const TileRuns &t, const uint32_t (&alive)[Q], const uint32_t (&base)[Q], uint32_t excl,
+                                                uint32_t room) {
+  const uint8_t *src = reinterpret_cast<const uint8_t *>(D.f.vals);
+  const int w = D.width;
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    if (!alive[q]) continue;
+    uint32_t run[4] = {t.span.lo, t.span.lo, t.span.lo, t.span.lo};
+    if (t.m) quad_runs(t, (static_cast<uint32_t>(q) * kSelectBlock + threadIdx.x) * 4u, run);
+    uint32_t r = base[q];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (!((alive[q] >> j) & 1u)) continue;
+      if (r < room) {
+        const size_t to = static_cast<size_t>(excl) + r;
+        const size_t from = run[j];
+        if (w == 16) *reinterpret_cast<SU64x2 *>(D.values + 16 * to) = *reinterpret_cast<const SU64x2 *>(src + 16 * from);
+        else *reinterpret_cast<SU64 *>(D.values + 8 * to) = *reinterpret_cast<const SU64 *>(src + 8 * from);
+        D.nulls[to] = static_cast<uint8_t>(run_valid(D.f, run[j]));
+      }
+      r++;
+    }
+  }
+}
+
 struct ExprConst {
   DVal y;
   FastDivisor fd;
@@ -120,10 +267,16 @@ __device__ __forceinline__ ExprConst expr_const(const FastOperands &f) {  // as 
 }
 
 // A dimension of a 4 / 2 / 1 byte slot: the tile's survivors, ranks [base[q] ..) per quad, local ranks below `room` only.
+template <bool RUNS>
 __device__ __forceinline__ void store_narrow_dim(const SelectDimD &D, int64_t row0, int n, const uint32_t (&alive)[Q], const uint32_t (&base)[Q],
-                                                 uint32_t excl, uint32_t room) {
+                                                 uint32_t excl, uint32_t room, const TileRuns *t) {
   uint32_t vals[Q][4], okb[Q];
-  load_column_tile(D.f, row0, n, vals, okb);
+  if constexpr (RUNS) {
+    if (t) load_runs_tile(D.f, *t, vals, okb);
+    else load_column_tile(D.f, row0, n, vals, okb);
+  } else {
+    load_column_tile(D.f, row0, n, vals, okb);
+  }
   const ExprConst c = expr_const(D.f);
   const int w = D.width;
 #pragma unroll
@@ -200,14 +353,24 @@ __device__ __forceinline__ void store_wide_dim(const SelectDimD &D, int64_t row0
   }
 }
 
-// (three workgroups per compute unit: 168 VGPRs, no scratch; a bound of four would spill)
-__global__ __launch_bounds__(kSelectBlock, 3) void select_scan_kernel(SelectPlanD p) {
+
+// RUNS: the plan reads a mode-3 column.  <false> is the kernel of plans without one, instruction for instruction: three
+// workgroups per compute unit, 168 VGPRs, no scratch (a bound of four would spill).  <true> spills 11 VGPRs at three, so it is
+// bound to two and keeps everything in registers.
+template <bool RUNS>
+__global__ __launch_bounds__(kSelectBlock, RUNS ? 2 : 3) void select_scan_kernel(SelectPlanD p) {
   __shared__ uint64_t sWave[kSelectBlock / 64];
   __shared__ uint32_t sTileExcl;
   __shared__ int sTile;
+  uint32_t *sEnds = nullptr;
+  if constexpr (RUNS) {
+    __shared__ uint32_t ends[kSelectTile];  // one column's run ends inside the tile, column after column
+    sEnds = ends;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = p.batchRows;
   uint32_t scanned = 0;  // (thread 0's copy is the one reported)
+  uint32_t rejectedTiles = 0, stagedTiles = 0;
   for (;;) {
     if (threadIdx.x == 0) {
       int t = static_cast<int>(atomicAdd(&p.state->ticket, 1u));
@@ -220,10 +383,13 @@ __global__ __launch_bounds__(kSelectBlock, 3) void select_scan_kernel(SelectPlan
       sTile = t;
     }
     __syncthreads();
-    const int tile = sTile;
+    const int tile = RUNS ? __builtin_amdgcn_readfirstlane(sTile) : sTile;  // (scalar: the run searches become scalar loads)
     if (tile < 0 || tile >= p.numTiles) break;
     const int64_t row0 = static_cast<int64_t>(tile) * kSelectTile;
     scanned++;
+    // mode-3 columns: the tile's first row and its last row inside the batch
+    const uint32_t urow0 = static_cast<uint32_t>(row0), lastRow = static_cast<uint32_t>(min(row0 + kSelectTile, static_cast<int64_t>(n)) - 1);
+    bool staged = false, rejected = false;
 
     // ---- the filter conjunction over the tile's rows
     uint32_t in[Q], alive[Q];
@@ -241,14 +407,50 @@ __global__ __launch_bounds__(kSelectBlock, 3) void select_scan_kernel(SelectPlan
     for (int k = 0; k < p.numFilters; k++) {
       const FastOperands &f = p.filters[k];
       uint32_t vals[Q][4], okb[Q], kb[Q];
-      load_column_tile(f, row0, n, vals, okb);
       DVal y;
       y.bits = f.bbits;
       y.ok = f.bok;
       y = cvt32(y, f.bkind, f.I);
+      if constexpr (RUNS) {
+        if (p.filterCounts[k]) {
+          const TileRuns t = tile_runs(p.filterCounts[k], p.filterRuns[k], urow0, lastRow, sEnds, staged);
+          if (t.m == 0) {  // one run decides for the whole tile (one value for every lane: made scalar, no vote)
+            const uint32_t v = __builtin_amdgcn_readfirstlane(run_value(f, t.span.lo)), ok = __builtin_amdgcn_readfirstlane(run_valid(f, t.span.lo));
+            if (compare_fast(f, v, ok, y)) continue;
+            rejected = true;
+            break;
+          }
+          load_runs_tile(f, t, vals, okb);
+        } else {
+          load_column_tile(f, row0, n, vals, okb);
+        }
+      } else {
+        load_column_tile(f, row0, n, vals, okb);
+      }
       compare_tile<Q>(f, vals, okb, in, y, kb);  // result validity is ignored (functor.hpp:903-915)
 #pragma unroll
       for (int q = 0; q < Q; q++) alive[q] &= kb[q];
+    }
+    if constexpr (RUNS) {
+      if (rejected) {
+        // No row of the tile survives and no other column is read.  The tile's word says so — as an inclusive prefix when the
+        // tile before has one already, so that chains of rejected tiles stay short for the look-back that crosses them — and
+        // the workgroup takes the next ticket; the batch's last tile goes on, empty, to publish the total.
+        rejectedTiles++;
+        if (tile != p.numTiles - 1) {
+          if (threadIdx.x == 0) {
+            uint64_t w = kFlagAggregate;
+            if (tile == 0) w = kFlagInclusive;
+            else if (const uint64_t before = ld_status(p.status + tile - 1); (before & kFlagMask) == kFlagInclusive) w = before;
+            st_status(p.status + tile, w);
+          }
+          if (staged) stagedTiles++;
+          __syncthreads();  // (sTile has been read by every wave before thread 0 writes the next)
+          continue;
+        }
+#pragma unroll
+        for (int q = 0; q < Q; q++) alive[q] = 0;
+      }
     }
 
     // ---- ranks in row order: quad q of every lane precedes quad q + 1 of any lane — four counts scanned as one word
@@ -298,16 +500,29 @@ __global__ __launch_bounds__(kSelectBlock, 3) void select_scan_kernel(SelectPlan
       const uint32_t room = p.limit - excl;
       for (int d = 0; d < p.numDims; d++) {
         const SelectDimD &D = p.dims[d];
-        if (D.width <= 4) store_narrow_dim(D, row0, n, alive, base, excl, room);
+        if constexpr (RUNS) {
+          if (D.counts) {
+            const TileRuns t = tile_runs(D.counts, D.runs, urow0, lastRow, sEnds, staged);
+            if (D.width <= 4) store_narrow_dim<true>(D, row0, n, alive, base, excl, room, &t);
+            else store_wide_runs(D, t, alive, base, excl, room);
+            continue;
+          }
+        }
+        if (D.width <= 4) store_narrow_dim<false>(D, row0, n, alive, base, excl, room, nullptr);
         else store_wide_dim(D, row0, alive, base, excl, room);
       }
     }
+    if (RUNS && staged) stagedTiles++;
     if (static_cast<uint64_t>(excl) + tileCount >= p.limit) break;  // nothing more is wanted
   }
 
   // ---- the last workgroup to leave publishes the result in the caller's pinned words
   if (threadIdx.x == 0) {
     if (scanned) atomicAdd(&p.state->scanned, scanned);
+    if constexpr (RUNS) {
+      if (rejectedTiles) atomicAdd(&p.state->rejected, rejectedTiles);
+      if (stagedTiles) atomicAdd(&p.state->staged, stagedTiles);
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     const uint32_t left = atomicAdd(&p.state->done, 1u);
     if (left == gridDim.x - 1) {
@@ -315,6 +530,10 @@ __global__ __launch_bounds__(kSelectBlock, 3) void select_scan_kernel(SelectPlan
       p.result[0] = ld_word(&p.state->stop) ? p.limit : ld_word(&p.state->total);
       p.result[1] = ld_word(&p.state->error);
       p.result[2] = ld_word(&p.state->scanned);
+      if constexpr (RUNS) {
+        p.result[3] = ld_word(&p.state->rejected);
+        p.result[4] = ld_word(&p.state->staged);
+      }
     }
   }
 }
@@ -324,7 +543,8 @@ struct NotFusable : std::runtime_error {
   explicit NotFusable(const std::string &why) : std::runtime_error("not fusable: " + why) {}
 };
 
-std::atomic<unsigned long long> g_stats[4];  // batches run, batches declined, tiles scanned, rows written
+std::atomic<unsigned long long> g_stats[4];     // batches run, batches declined, tiles scanned, rows written
+std::atomic<unsigned long long> g_runStats[2];  // tiles rejected by a run, tiles that staged run ends
 
 bool select_enabled() {
   static EnvSwitch<bool> on("ARES_SELECT", [](const char *e) { return !(e && e[0] == '0'); });
@@ -332,17 +552,18 @@ bool select_enabled() {
 }
 
 // workgroups of one launch: as many as the device holds at once; ARES_SELECT_GRID=n (tests) overrides
-int select_grid(int device) {
+int select_grid(int device, bool runs) {
   static EnvSwitch<int> forced("ARES_SELECT_GRID", [](const char *e) { return e ? atoi(e) : 0; });
   const int f = forced.get();
   if (f > 0) return std::min(f, kSelectGridCap);
   static std::mutex mu;
-  static std::map<int, int> known;
+  static std::map<std::pair<int, bool>, int> known;
   std::lock_guard<std::mutex> lock(mu);
-  auto it = known.find(device);
+  auto it = known.find({device, runs});
   if (it != known.end()) return it->second;
   int perCU = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, reinterpret_cast<const void *>(&select_scan_kernel), kSelectBlock, 0) != hipSuccess || perCU < 1) {
+  const void *kernel = runs ? reinterpret_cast<const void *>(&select_scan_kernel<true>) : reinterpret_cast<const void *>(&select_scan_kernel<false>);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, kSelectBlock, 0) != hipSuccess || perCU < 1) {
     (void)hipGetLastError();
     perCU = 4;
   }
@@ -350,20 +571,38 @@ int select_grid(int device) {
     (void)hipGetLastError();
     cus = 256;
   }
-  return known[device] = std::max(1, std::min(perCU * cus, kSelectGridCap));
+  return known[{device, runs}] = std::max(1, std::min(perCU * cus, kSelectGridCap));
 }
 
 bool wide_type(int t) { return t == Int64 || t == Uint64 || t == GeoPoint || t == UUID; }
+
+// the run-length layout [counts][validity][values] (binding.hpp: mode 3)
+bool run_length_layout(const VectorPartySlice &vp) { return vp.BasePtr && vp.ValuesOffset != 0 && vp.NullsOffset != 0; }
 
 void check_column(const AresFusedExpr &e, int batchRows) {
   if (e.arity != 1 && e.arity != 2) throw NotFusable("arity");
   if (e.lhs.Type != VectorPartyInput || (e.arity == 2 && e.rhs.Type != ConstantInput))
     throw NotFusable("operands must be a main-table column and a constant");
-  if (static_cast<int64_t>(e.lhs.Vector.VP.Length) < batchRows) throw NotFusable("column shorter than the batch");
+  const VectorPartySlice &vp = e.lhs.Vector.VP;
+  if (run_length_layout(vp)) {
+    // Length is the number of runs; the rows the runs cover are known to the counts only (the per-node sequence does not
+    // check them either: rows past the last count take the last run)
+    if (vp.Length < 1) throw NotFusable("run-length column without runs");
+    if (vp.DataType == GeoPoint) throw NotFusable("run-length GeoPoint column (read undecoded by the per-node sequence)");
+    if (reinterpret_cast<uintptr_t>(vp.BasePtr) & 3u) throw NotFusable("run-length counts are not word-aligned");
+    return;
+  }
+  if (static_cast<int64_t>(vp.Length) < batchRows) throw NotFusable("column shorter than the batch");
 }
 
+// the run description of a bound mode-3 column
+struct RunsOf {
+  const uint32_t *counts = nullptr;
+  uint32_t runs = 0;
+};
+
 // a filter, or a dimension of a 4 / 2 / 1 byte slot: the operand shape of the fast transform / filter kernels
-FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream) {
+FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream, RunsOf &runs) {
   check_column(e, batchRows);
   if (wide_type(e.lhs.Vector.VP.DataType)) throw NotFusable("expression over a wide column");
   InputVector ins[2] = {e.lhs, e.arity == 2 ? e.rhs : e.lhs};
@@ -374,6 +613,14 @@ FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batch
   } catch (const std::invalid_argument &bad) {
     throw NotFusable(bad.what());
   }
+  runs = RunsOf();
+  if (p.a.type == OP_COLUMN && p.a.mode == 3) {
+    // Bound here, not by the deferral machinery's fast_operands(): the expression shapes are the ones it takes for a column
+    // with validity (same kinds, widths and functors), and vals / nulls name the RUN arrays
+    runs.counts = reinterpret_cast<const uint32_t *>(p.a.base);
+    runs.runs = p.a.length;
+    p.a.mode = 2;
+  }
   FastOperands f;
   if (!fast_operands(p, f, compareOnly)) throw NotFusable("expression shape");
   f.idx = nullptr;
@@ -382,7 +629,7 @@ FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batch
 }
 
 // a bare Int64 / GeoPoint / UUID column into a slot of its own type
-FastOperands wide_operands(const AresFusedExpr &e, int batchRows, hipStream_t stream) {
+FastOperands wide_operands(const AresFusedExpr &e, int batchRows, hipStream_t stream, RunsOf &runs) {
   check_column(e, batchRows);
   const int t = e.lhs.Vector.VP.DataType;
   if (e.arity != 1 || e.functor != Noop) throw NotFusable("expression over a wide column");
@@ -394,11 +641,16 @@ FastOperands wide_operands(const AresFusedExpr &e, int batchRows, hipStream_t st
   } catch (const std::invalid_argument &bad) {
     throw NotFusable(bad.what());
   }
-  if (op.type != OP_COLUMN || op.mode > 2) throw NotFusable("column mode");
+  if (op.type != OP_COLUMN || op.mode > 3) throw NotFusable("column mode");
+  runs = RunsOf();
+  if (op.mode == 3) {
+    runs.counts = reinterpret_cast<const uint32_t *>(op.base);
+    runs.runs = op.length;
+  }
   FastOperands f;
   memset(&f, 0, sizeof(f));
   f.vals = reinterpret_cast<const uint32_t *>(op.base + op.valuesOff);
-  f.nulls = op.mode == 2 ? op.base + op.nullsOff : nullptr;
+  f.nulls = op.mode >= 2 ? op.base + op.nullsOff : nullptr;
   f.bitOff = op.bitOff;
   f.akind = op.kind;
   f.arity = 1;
@@ -424,7 +676,14 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
   memset(&plan, 0, sizeof(plan));
   plan.numFilters = q.numFilters;
   plan.numDims = q.numDims;
-  for (int k = 0; k < q.numFilters; k++) plan.filters[k] = narrow_operands(q.filters[k], true, batchRows, stream);
+  bool anyRuns = false;
+  RunsOf runs;
+  for (int k = 0; k < q.numFilters; k++) {
+    plan.filters[k] = narrow_operands(q.filters[k], true, batchRows, stream, runs);
+    plan.filterCounts[k] = runs.counts;
+    plan.filterRuns[k] = runs.runs;
+    anyRuns |= runs.counts != nullptr;
+  }
   const size_t capacity = static_cast<size_t>(outKeys.VectorCapacity > 0 ? outKeys.VectorCapacity : 0);
   for (int d = 0; d < q.numDims; d++) {
     const int t = q.dims[d].outType;
@@ -434,12 +693,15 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
     D.width = step_in_bytes(t);
     if (D.width != L.width[d]) throw NotFusable("dimension vector layout");
     if (narrow) {
-      D.f = narrow_operands(q.dims[d], false, batchRows, stream);
+      D.f = narrow_operands(q.dims[d], false, batchRows, stream, runs);
       if (D.width < 4 && !(D.f.rk == K_I32 || D.f.rk == K_U32)) throw NotFusable("float result into a narrow slot");
       D.outKind = t == Int32 ? K_I32 : t == Uint32 ? K_U32 : K_F32;
     } else {
-      D.f = wide_operands(q.dims[d], batchRows, stream);
+      D.f = wide_operands(q.dims[d], batchRows, stream, runs);
     }
+    D.counts = runs.counts;
+    D.runs = runs.runs;
+    anyRuns |= runs.counts != nullptr;
     D.values = outKeys.DimValues + static_cast<size_t>(L.valueOff[d]) * capacity;
     D.nulls = outKeys.DimValues + static_cast<size_t>(L.valueBytes) * capacity + static_cast<size_t>(d) * capacity;
   }
@@ -448,15 +710,16 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
   if (wanted > 0 && !outKeys.DimValues) throw std::invalid_argument("null dimension vector");
   if (wanted == 0) return 0;
 
-  // a 4-byte column that the plan reads once is loaded non-temporally
+  // a 4-byte column that the plan reads once is loaded non-temporally (modes 1/2: the run arrays of a mode-3 column are
+  // small and read again and again)
   auto uses = [&](const uint32_t *vals) {
     int c = 0;
     for (int k = 0; k < plan.numFilters; k++) c += plan.filters[k].vals == vals;
     for (int d = 0; d < plan.numDims; d++) c += plan.dims[d].f.vals == vals;
     return c;
   };
-  for (int k = 0; k < plan.numFilters; k++) plan.filters[k].streaming = uses(plan.filters[k].vals) == 1;
-  for (int d = 0; d < plan.numDims; d++) plan.dims[d].f.streaming = uses(plan.dims[d].f.vals) == 1;
+  for (int k = 0; k < plan.numFilters; k++) plan.filters[k].streaming = !plan.filterCounts[k] && uses(plan.filters[k].vals) == 1;
+  for (int d = 0; d < plan.numDims; d++) plan.dims[d].f.streaming = !plan.dims[d].counts && uses(plan.dims[d].f.vals) == 1;
 
   flush_deferred_for_vector(device, outKeys, nullptr, 0);
   grouped_note_write(device, outKeys);
@@ -473,9 +736,10 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
   plan.result = const_cast<uint32_t *>(result);
   result[0] = 0u;
   result[1] = 2u;  // (overwritten by the launch's last workgroup)
-  result[2] = 0u;
-  const int grid = std::min(select_grid(device), plan.numTiles);
-  ARES_LAUNCH("select_scan_kernel", select_scan_kernel, grid, kSelectBlock, stream, plan);
+  result[2] = result[3] = result[4] = 0u;
+  const int grid = std::min(select_grid(device, anyRuns), plan.numTiles);
+  if (anyRuns) ARES_LAUNCH("select_scan_kernel", (select_scan_kernel<true>), grid, kSelectBlock, stream, plan);
+  else ARES_LAUNCH("select_scan_kernel", (select_scan_kernel<false>), grid, kSelectBlock, stream, plan);
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   ws.mark_idle();
   if (result[1] == 2u) throw AlgorithmError("ERROR: select scan: the launch finished without publishing its result");
@@ -484,6 +748,8 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
   g_stats[0]++;
   g_stats[2] += result[2];
   g_stats[3] += rows;
+  g_runStats[0] += result[3];
+  g_runStats[1] += result[4];
   mem_note_dim_rows(device, outKeys, 0, rows);
   return static_cast<int>(rows);
 }
@@ -508,4 +774,9 @@ extern "C" CGoCallResHandle AresFusedFilterSelect(const AresFusedSelect *query, 
 extern "C" void AresSelectStats(unsigned long long *counters) {
   if (!counters) return;
   for (int i = 0; i < 4; i++) counters[i] = ares::g_stats[i].load();
+}
+
+extern "C" void AresSelectRunStats(unsigned long long *counters) {
+  if (!counters) return;
+  for (int i = 0; i < 2; i++) counters[i] = ares::g_runStats[i].load();
 }

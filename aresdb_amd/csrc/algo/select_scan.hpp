@@ -19,9 +19,13 @@ constexpr int kSelectGridCap = 2048;
 
 // One dimension of the plan.  width 4 / 2 / 1: `f` is the expression (column pointers included) and the slot receives what
 // the transform kernels store for it; width 8 / 16: a bare column, f.vals / f.nulls / f.bitOff name it and the slot receives
-// the row's stored bytes.
+// the row's stored bytes.  A run-length (mode 3) column: `counts` is non-null, f.vals / f.nulls are the RUN arrays (value and
+// validity bit of run r at index r, bit r + f.bitOff) and row r of the batch lies in the run locate() (device_model.hpp) gives.
 struct SelectDimD {
   FastOperands f;
+  const uint32_t *counts;  // mode 3: counts[0 .. runs], counts[r] = first row of run r; nullptr for modes 1/2
+  uint32_t runs;           // mode 3: number of runs (VectorPartySlice::Length), at least 1
+  uint32_t pad;
   uint8_t *values;  // the slot's first row
   uint8_t *nulls;   // its validity bytes
   int width;        // bytes per row of the slot: 16, 8, 4, 2 or 1
@@ -36,19 +40,22 @@ struct SelectStateD {
   uint32_t stop;     // some tile's inclusive prefix has reached the limit
   uint32_t total;    // inclusive prefix of the batch's last tile
   uint32_t scanned;  // tiles whose columns were read
-  uint32_t pad[2];
+  uint32_t rejected;  // of those: thrown away by ONE run of a mode-3 filter column that is null or fails the comparison
+  uint32_t staged;    // of those: tiles that staged the run ends of some mode-3 column in LDS (several runs in the tile)
 };
 static_assert(sizeof(SelectStateD) == 32, "the state block is cleared as a whole and the status words follow it");
 
 struct SelectPlanD {
   int numFilters, numDims;
   FastOperands filters[kSelectFilters];
+  const uint32_t *filterCounts[kSelectFilters];  // mode-3 filter columns, as SelectDimD::counts / runs (FastOperands is pinned
+  uint32_t filterRuns[kSelectFilters];           // at 80 bytes: the generated kernels' host code reads it)
   SelectDimD dims[kSelectDims];
   int batchRows, numTiles;
   uint32_t limit;  // 0xFFFFFFFF: none
   SelectStateD *state;
   uint64_t *status;   // one look-back word per tile
-  uint32_t *result;   // mapped pinned words of the calling thread: {rows, error, tiles scanned}
+  uint32_t *result;   // mapped pinned words of the calling thread: {rows, error, tiles scanned, rejected, staged}
 };
 
 }  // namespace ares

@@ -134,15 +134,33 @@ def run_select_native(be, plan, batches):
     """A non-aggregation query through the C++ driver: (rows, per-dimension value bytes, validity bytes, fused batches)."""
     from .driver import NativeQuery
     q = NativeQuery(be, plan, list(batches[0][0].keys()))
-    for cols, valid in batches:
-        dev = {k: DeviceColumn(be, t, v, valid=valid[k]) for k, (t, v) in cols.items()}
-        q.run({k: d.vp for k, d in dev.items()}, len(next(iter(cols.values()))[1]))
+    for cols, valid, *rest in batches:  # (an archive-shaped batch brings {column: run-length counts}: archive_batch)
+        counts = rest[0] if rest else {}
+        dev = {k: DeviceColumn(be, t, v, valid=valid[k], counts=counts.get(k)) for k, (t, v) in cols.items()}
+        n = max(len(v) if k not in counts else int(counts[k][-1]) for k, (t, v) in cols.items())
+        q.run({k: d.vp for k, d in dev.items()}, n)
         for d in dev.values():
             d.free()
     dims, valids, _ = q.fetch()
     out = (q.result_size, [bytes(d) for d in dims], [bytes(v) for v in valids], q.fused_batches)
     q.release()
     return out
+
+
+def archive_batch(cols, valid, key):
+    """The batch sorted by column `key` (nulls first), that column packed run-length as an archive batch stores its sort
+    column — counts, a validity bit and a value per run: (cols, valid, {key: counts})."""
+    t, v = cols[key]
+    ok = np.ones(len(v), bool) if valid[key] is None else np.asarray(valid[key], bool)
+    order = np.lexsort((v, ok))
+    cols = {k: (tt, vv[order]) for k, (tt, vv) in cols.items()}
+    valid = {k: (None if x is None else np.asarray(x)[order]) for k, x in valid.items()}
+    v, ok = v[order], ok[order]
+    head = np.ones(len(v), bool)
+    head[1:] = (v[1:] != v[:-1]) | (ok[1:] != ok[:-1])
+    starts = np.flatnonzero(head)
+    cols[key], valid[key] = (t, v[starts]), ok[starts]
+    return cols, valid, {key: np.concatenate([starts, [len(v)]]).astype(np.uint32)}
 
 
 def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
@@ -164,3 +182,10 @@ def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
     assert plain[0] == n + 100 and plain[3] == 0 and fused[3] == 2, (plain[0], plain[3], fused[3])
     assert fused[:3] == plain[:3], "the fused select scan and the ordinary sequence disagree"
     assert plain[:3] == want[:3], "the select query disagrees with the oracle"
+    # the same select over archive-shaped batches (sorted by d1, d1 run-length): every batch through the select scan, which
+    # reads the runs where they lie, and the rows of the ordinary sequence
+    arch = [archive_batch(cols, valid, "d1") for cols, valid in data]
+    plain = run_select_native(hip, select_plan(columns, filters, -1), arch)
+    fused = run_select_native(hip, select_plan(columns, filters, -1, use_fused_extension=True), arch)
+    assert plain[0] > 0 and plain[3] == 0 and fused[3] == batches, (plain[0], plain[3], fused[3])
+    assert fused[:3] == plain[:3], "the fused select scan and the ordinary sequence disagree on archive-shaped batches"

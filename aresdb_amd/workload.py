@@ -117,10 +117,11 @@ def _pack_run_length(values: torch.Tensor, valid: Optional[torch.Tensor], data_t
     bitmap = (run_ok.view(nb, 8) * weights).sum(dim=1, dtype=torch.int32).to(torch.uint8)
     nulls_off = _align64(4 * (runs + 1))
     values_off = nulls_off + _align64(nb)
-    blob = torch.zeros(values_off + _align64(4 * runs), dtype=torch.uint8, device=values.device)
+    raw = values[starts.long()].contiguous().view(torch.uint8)  # (4 bytes per run, or 2 / 1 for the narrow types)
+    blob = torch.zeros(values_off + _align64(raw.numel()), dtype=torch.uint8, device=values.device)
     blob[:4 * (runs + 1)] = counts.view(torch.uint8)
     blob[nulls_off:nulls_off + nb] = bitmap
-    blob[values_off:values_off + 4 * runs] = values[starts.long()].contiguous().view(torch.uint8)
+    blob[values_off:values_off + raw.numel()] = raw
     return RunLengthColumn(blob, values_off, data_type, n, True, runs, nulls_off, values, valid)
 
 

@@ -190,11 +190,19 @@ CGoCallResHandle AresFusedFilterHashReduce(const AresFusedQuery *query, int batc
  *
  * Shapes accepted (anything else returns an error string starting with "not fusable" before anything is launched, and the
  * host simply runs the ordinary sequence): 0-4 filters, each a comparison of a main-table column (1-, 2- or 4-byte type,
- * modes 1/2) with a constant; 1-8 dimensions in vector order (dims[d] is slot d of outKeys, widths descending), each either
+ * modes 1/2/3) with a constant; 1-8 dimensions in vector order (dims[d] is slot d of outKeys, widths descending), each either
  * a main-table column of a 1-, 2- or 4-byte type, bare or combined with a constant by a binary functor, into a slot of
  * 4 / 2 / 1 bytes (outType = the slot's DataType; a narrow slot takes integer results), or a BARE Int64 / GeoPoint / UUID
- * column (modes 1/2) into a slot of its own type.  Declined: Bool and Uint64 columns, mode 0 / 3 columns, foreign-table and
- * array operands, expressions over a wide column.  outKeys.VectorCapacity must be at least batchRows (limit < 0) or
+ * column (modes 1/2; Int64 and UUID mode 3 as well) into a slot of its own type.
+ * Mode 3 is the run-length layout of an archive batch's sort columns, [counts u32 x (Length + 1)][validity bit per run]
+ * [value per run] with Length = the number of runs (at least 1): rows are raw rows (no base counts, start count 0), row r
+ * lies in the run whose [counts[k], counts[k + 1]) holds it, rows past the last count take the last run, and counts[Length]
+ * is not read — what the per-node sequence does.  The runs are located inside each 4096-row tile, so the limit's early out
+ * holds for archive batches too, and a tile that lies inside ONE run of a filter column that is null or fails the comparison
+ * is thrown away without reading any other column (AresSelectRunStats counts them).
+ * Declined: Bool and Uint64 columns, mode 0 columns, a GeoPoint column in the mode-3 layout (the per-node sequence never
+ * decodes one: it reads it row by row as a mode-2 column), a mode-3 column without runs, foreign-table and array operands,
+ * expressions over a wide column.  outKeys.VectorCapacity must be at least batchRows (limit < 0) or
  * min(batchRows, limit); batchRows == 0 or limit == 0 returns 0 and launches nothing.
  * Environment (both obey AresReloadEnv): ARES_SELECT=0 declines always; ARES_SELECT_GRID=n (tests) sets the number of
  * workgroups, at most 2048. */
@@ -209,6 +217,9 @@ CGoCallResHandle AresFusedFilterSelect(const AresFusedSelect *query, int batchRo
                                        DimensionVector outKeys, void *cudaStream, int device);
 /* {batches run, batches declined, tiles scanned, rows written} since process start */
 void AresSelectStats(unsigned long long *counters);
+/* {tiles rejected by one run of a run-length filter column, tiles that staged run ends in LDS} since process start; both are
+ * counted among the tiles scanned */
+void AresSelectRunStats(unsigned long long *counters);
 
 #ifdef __cplusplus
 }

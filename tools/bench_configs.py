@@ -322,6 +322,90 @@ def select_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000,
     return out
 
 
+def select_archive_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1), city=7):
+    """select_leg's query plus city_id == `city` over ARCHIVE-shaped batches: every batch of the trips shard sorted by
+    (city_id, status) and those two columns packed run-length (workload._pack_run_length), as an archive batch stores its
+    sort columns.  Ordinary sequence and AresFusedFilterSelect on the same build, rows compared as select_leg compares them.
+    One JSON row per (limit, path) with the tiles scanned, rejected by a run of a filter column, and staged in LDS."""
+    from aresdb_amd import trips
+    from aresdb_amd.executor import Binary, Const
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(12)
+    batches = []
+    for b in trips.trips_shard(rows, batch_rows, seed=11, device=dev):
+        n = b["fare"].length
+        key = trips.key_column(n, gen, dev)
+        vals = {k: trips.column_values(b[k]) for k, _ in trips.COLUMNS}
+        ok = {k: b[k].valid() for k, _ in trips.COLUMNS}
+        code = lambda k: torch.where(ok[k], vals[k].to(torch.int64) + 1, torch.zeros((), dtype=torch.int64, device=dev))
+        order = torch.argsort(code("city_id") * 256 + code("status"), stable=True)
+        out = {}
+        for k, dt in trips.COLUMNS:
+            v, o = vals[k][order], ok[k][order]
+            out[k] = workload._pack_run_length(v, o, dt) if k in ("city_id", "status") else trips._pack(v, o, dt)
+        k64 = key.blob[key.values_off:key.values_off + 16 * n].view(torch.int64).view(n, 2)
+        kraw = torch.stack([k64[:, 0][order], k64[:, 1][order]], dim=1).reshape(-1).view(torch.uint8)
+        kok = key.valid()[order].to(torch.uint8)
+        nb = (n + 7) // 8
+        if nb * 8 != n:
+            kok = torch.cat([kok, torch.zeros(nb * 8 - n, dtype=torch.uint8, device=dev)])
+        weights = (1 << torch.arange(8, device=dev, dtype=torch.int32)).to(torch.uint8)
+        off = workload._align64(nb)
+        blob = torch.zeros(off + kraw.numel() + 64, dtype=torch.uint8, device=dev)
+        blob[:nb] = (kok.view(nb, 8) * weights).sum(dim=1, dtype=torch.int32).to(torch.uint8)
+        blob[off:off + kraw.numel()] = kraw
+        out["key"] = workload.ResidentColumn(blob, off, abi.UUID, n, True)
+        batches.append(out)
+        del vals, ok, order, key, k64, kraw, kok, b
+    names = [n for n, _ in trips.COLUMNS] + ["key"]
+    vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+    runs = {k: sum(b[k].runs for b in batches) for k in ("city_id", "status")}
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    out, first = [], {}
+    for limit in limits:
+        for fused in (False, True):
+            plan = trips.trips_select_plan(limit=limit, fused=fused)
+            plan.filters.insert(0, Binary(abi.Equal, Col("city_id"), Const(int(city))))
+            packed = None
+            def run():
+                nonlocal packed
+                q = NativeQuery(be, plan, names, streams=streams)
+                q.set_max_batch_size(batch_rows)
+                if packed is None:
+                    packed = q.pack_batches(vps)
+                q.run_batches(packed)
+                return q
+            run().release()
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps):
+                q = run(); q.release()
+            torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+            be.profiler_enable(True)
+            stats0, runs0 = be.select_stats(), be.select_run_stats()
+            q = run(); torch.cuda.synchronize()
+            kernels = be.profiler_report(); be.profiler_enable(False)
+            stats1, runs1 = be.select_stats(), be.select_run_stats()
+            n, fused_batches = q.result_size, q.fused_batches
+            dims, valids, _ = q.fetch()
+            q.release()
+            head = [bytes(d[:w * min(n, 1000000)]) for d, w in zip(dims, (4, 2, 4, 16))] + [bytes(v[:min(n, 1000000)]) for v in valids]
+            del dims, valids
+            check = "first"
+            if not fused:
+                first[limit] = (n, head)
+            else:
+                check = "ok" if first[limit] == (n, head) else "MISMATCH against the ordinary sequence"
+            kernel_ms = sum(ms for c, ms in kernels.values())
+            out.append({"config": "selectarchive", "limit": limit, "path": "extension" if fused else "ordinary", "rows": rows, "batches": len(vps),
+                        "batch_rows": batch_rows, "city": city, "cities": trips.CITIES, "runs": runs, "result_rows": n, "fused_batches": fused_batches,
+                        "check": check, "tiles": sum((r + 4095) // 4096 for _, r in vps), "tiles_scanned": stats1["tiles"] - stats0["tiles"],
+                        "tiles_rejected": runs1["rejected"] - runs0["rejected"], "tiles_staged": runs1["staged"] - runs0["staged"],
+                        "ms_per_step": dt * 1e3, "ms_per_1B_rows": dt * 1e3 * 1e9 / rows, "kernel_ms_per_step": kernel_ms,
+                        "kernel_ms_per_1B_rows": kernel_ms * 1e9 / rows,
+                        "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
+    return out
+
+
 def wide_key_legs(be, dev, which, rows, batch_rows=1 << 26, steps=3):
     """Sort + Reduce over group keys in dimension slots of 8 and 16 bytes (rows of such a query exist when Sort arrives: a
     transform into a wide slot runs at once), through the C++ driver in the Go call order, COUNT(*):
@@ -617,6 +701,9 @@ def main():
     if "select" in which:  # SELECT_BATCH_ROWS / SELECT_LIMITS (comma separated, -1 = none): other batch sizes, fewer limits
         res += select_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                           limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
+    if "selectarchive" in which:  # the same switches as "select"
+        res += select_archive_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
+                                  limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
     for leg in ("c3int64", "uuid"):
         if leg in which: res += wide_key_legs(be, dev, leg, int(float(os.environ.get("WIDE_ROWS", str(1 << 28)))))
     if "c3sortfloat" in which: res += sort_float_leg(be, dev, int(float(os.environ.get("SORT_FLOAT_ROWS", "1e9"))))
