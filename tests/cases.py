@@ -551,6 +551,92 @@ class GroupByCase:
         return np.uint64 if self.vb == 8 else np.uint32
 
 
+_SLOT_NP = {4: np.uint32, 2: np.uint16, 1: np.uint8}
+
+
+class ResultVectors:
+    """The two (dimension vector, measure vector) pairs a query ping-pongs between: [0] holds the previous result with the
+    batch behind it and is HashReduce's input, [1] is its output; swap() after every batch."""
+
+    def __init__(self, be, ndw, capacity, value_dtype):
+        self.be, self.capacity, self.value_dtype = be, capacity, np.dtype(value_dtype)
+        self.vb = self.value_dtype.itemsize
+        self.dims = [H.DimVector(be, capacity, ndw, with_hash=False, with_index=False) for _ in range(2)]
+        self.meas = [H.Buf(be, nbytes=self.vb * capacity + 8) for _ in range(2)]
+
+    def keys(self, which, g):
+        """the first g dimension rows as (values, validity bytes) tuples — reads the dimension vector only"""
+        blob = self.dims[which].values.read(np.uint8)
+        cols, oks = [], []
+        for vo, no, w in self.dims[which].dim_offsets():
+            cols.append(blob[vo:vo + g * w].view(_SLOT_NP[w]).tolist())
+            oks.append(blob[no:no + g].tolist())
+        return list(zip(zip(*cols), zip(*oks))) if g else []
+
+    def result(self, which, g):
+        """({key: value}, keys in vector order) of the first g rows"""
+        keys = self.keys(which, g)
+        return dict(zip(keys, self.meas[which].read(self.value_dtype, g).tolist())), keys
+
+    def hash_reduce(self, length, agg):
+        g = self.be.call("HashReduce", self.dims[0].struct(), self.meas[0].ptr, self.dims[1].struct(), self.meas[1].ptr, self.vb,
+                         length, agg, None, 0)
+        self.be.wait()
+        return g
+
+    def swap(self):
+        self.dims.reverse()
+        self.meas.reverse()
+
+    def free(self):
+        for x in self.dims + self.meas:
+            x.free()
+
+
+class ExplicitGroupBy:
+    """GroupByCase's sibling for rows that are GIVEN, not drawn: one or more batches of (dimension rows, validity rows,
+    measure values) through HashReduce the way the Go host issues it — every batch is written behind the previous result
+    in the input vectors, reduced into the other pair of vectors, and the pairs are swapped.
+    rows / valids: per batch a sequence of tuples, one entry per dimension in vector order; values: per batch a numpy array
+    of `value_dtype`."""
+
+    def __init__(self, ndw, batches, agg, value_dtype, capacity_slack=3):
+        self.ndw = tuple(ndw)
+        self.widths = [w for w, c in zip(H.DIM_WIDTHS, self.ndw) for _ in range(c)]
+        self.agg, self.value_dtype = agg, np.dtype(value_dtype)
+        self.vb = self.value_dtype.itemsize
+        self.batches = []
+        for rows, valids, values in batches:
+            n = len(rows)
+            assert len(valids) == n and len(values) == n
+            rows = np.asarray(rows, dtype=np.uint64).reshape(n, len(self.widths))
+            valids = np.asarray(valids, dtype=np.uint8).reshape(n, len(self.widths))
+            cols = [np.ascontiguousarray(rows[:, d].astype(_SLOT_NP[w])).view(np.uint8) for d, w in enumerate(self.widths)]
+            self.batches.append((cols, [np.ascontiguousarray(valids[:, d]) for d in range(len(self.widths))],
+                                 np.ascontiguousarray(np.asarray(values).astype(self.value_dtype)).view(np.uint8), n))
+        self.capacity = sum(b[3] for b in self.batches) + capacity_slack
+
+    def run_hash_reduce(self, be):
+        """One dict per batch: groups, the key -> value map, the keys in output order."""
+        v = ResultVectors(be, self.ndw, self.capacity, self.value_dtype)
+        offs = v.dims[0].dim_offsets()
+        out, size = [], 0
+        for cols, oks, values, n in self.batches:
+            for d, (vo, no, w) in enumerate(offs):
+                if n:
+                    v.dims[0].values.write(cols[d], offset=vo + size * w)
+                    v.dims[0].values.write(oks[d], offset=no + size)
+            if n:
+                v.meas[0].write(values, offset=self.vb * size)
+            g = v.hash_reduce(size + n, self.agg)
+            table, keys = v.result(1, g)
+            out.append({"groups": g, "map": table, "keys": keys})
+            size = g
+            v.swap()
+        v.free()
+        return out
+
+
 class HllCase:
     """Several batches through HyperLogLog, replaying the Go host's protocol
     (query/aql_batchexecutor.go:219-233, query/aql_processor.go:717-723): dimension rows of the
