@@ -151,6 +151,18 @@ class FusedSelect(C.Structure):
                 ("dims", FusedExpr * 8)]
 
 
+class FusedJoin(C.Structure):
+    """AresFusedJoin (include/ares_extensions.h): one join of AresFusedFilterJoinSelect"""
+    _fields_ = [("key", InputVector), ("index", CuckooHashIndex)]
+
+
+class FusedJoinSelect(C.Structure):
+    """AresFusedJoinSelect (include/ares_extensions.h): the query of AresFusedFilterJoinSelect"""
+    _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("numJoins", C.c_int), ("joins", FusedJoin * 2),
+                ("numForeignFilters", C.c_int), ("foreignFilters", FusedExpr * 4), ("foreignFilterJoin", C.c_int * 4),
+                ("numDims", C.c_int), ("dims", FusedExpr * 8), ("dimJoin", C.c_int * 8)]
+
+
 # sizes pinned by include/ares_algorithm.h's static assertions (SURVEY.md 8b)
 ABI_SIZES = {CGoCallResHandle: 16, RecordID: 8, CuckooHashIndex: 40, DefaultValue: 24,
              VectorPartySlice: 56, ScratchSpaceVector: 16, ConstantVector: 24,
@@ -304,6 +316,24 @@ class Backend:
         self._algo.AresSelectStats.argtypes, self._algo.AresSelectStats.restype = [C.POINTER(C.c_ulonglong)], None
         self._algo.AresSelectStats(c)
         return {"batches": int(c[0]), "declined": int(c[1]), "tiles": int(c[2]), "rows": int(c[3])}
+
+    @property
+    def has_fused_join_select(self):
+        return hasattr(self._algo, "AresFusedFilterJoinSelect")
+
+    def fused_filter_join_select(self, query, batch_rows, limit, out_keys, stream=None, device=0):
+        """AresFusedFilterJoinSelect: rows written (AresError, "not fusable: ..." among them, as every call)."""
+        fn = self._algo.AresFusedFilterJoinSelect  # AttributeError: this library has no such entry point
+        fn.argtypes = [C.POINTER(FusedJoinSelect), C.c_int, C.c_int, DimensionVector, _S, _I]
+        fn.restype = CGoCallResHandle
+        return _check(fn(C.byref(query), int(batch_rows), int(limit), out_keys, stream, device))
+
+    def select_join_stats(self):
+        """{batches, declined, tiles, rows, probed} of AresFusedFilterJoinSelect since the process started."""
+        c = (C.c_ulonglong * 5)()
+        self._algo.AresSelectJoinStats.argtypes, self._algo.AresSelectJoinStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresSelectJoinStats(c)
+        return {"batches": int(c[0]), "declined": int(c[1]), "tiles": int(c[2]), "rows": int(c[3]), "probed": int(c[4])}
 
     def select_run_stats(self):
         """{rejected, staged}: tiles of AresFusedFilterSelect thrown away by one run of a run-length filter column, and tiles

@@ -279,6 +279,35 @@ __device__ __forceinline__ DVal read_stored32(const uint8_t *values, int kind, i
   return r;
 }
 
+// value of a joined (OP_FOREIGN) operand at record `rid` (query/iterator.hpp:911-930): a missing record, a batch outside the
+// table and an index at or past the last batch's records give (0, null); a mode-0 batch gives the default
+__device__ __forceinline__ DVal load_foreign32(const OperandD &op, RecordID rid) {
+  DVal r;
+  r.bits = 0;
+  r.ok = 0;
+  if (rid.batchID != 0 && (rid.batchID - op.baseBatchID < op.numBatches - 1 ||
+                           rid.index < static_cast<uint32_t>(op.numRecLast))) {
+    const ForeignBatchD b = op.batches[rid.batchID - op.baseBatchID];
+    if (b.isConst) {
+      r.bits = op.cbits;
+      r.ok = op.cok;
+      return r;
+    }
+    const uint32_t p = rid.index;
+    r = read_stored32(b.base + b.valuesOff, op.kind, op.step, p, p + b.bitOff);
+    r.ok = b.valuesOff != 0 ? get_bit(b.base + b.nullsOff, p + b.bitOff) : 1u;
+    if (op.tz) {  // enum -> utc offset (query/iterator.hpp:894-908)
+      DVal e = cvt32(r, op.kind, K_I32);
+      const int32_t ev = static_cast<int32_t>(e.bits);
+      DVal t;
+      t.ok = r.ok;
+      t.bits = ev < op.tzSize ? static_cast<uint32_t>(static_cast<int32_t>(op.tz[ev])) : 0u;
+      r = cvt32(t, K_I32, op.kind);
+    }
+  }
+  return r;
+}
+
 // value of a 32-bit-kind operand at output position i (row = indexVector[i] for columns)
 __device__ __forceinline__ DVal load32(const OperandD &op, uint32_t i, uint32_t row, const uint32_t *baseCounts,
                                        uint32_t startCount) {
@@ -298,32 +327,8 @@ __device__ __forceinline__ DVal load32(const OperandD &op, uint32_t i, uint32_t 
       r.ok = op.mode >= 2 ? get_bit(op.base + op.nullsOff, p + op.bitOff) : 1u;
       return r;
     }
-    default: {  // OP_FOREIGN (query/iterator.hpp:911-930)
-      const RecordID rid = op.rids[i];
-      r.bits = 0;
-      r.ok = 0;
-      if (rid.batchID != 0 && (rid.batchID - op.baseBatchID < op.numBatches - 1 ||
-                               rid.index < static_cast<uint32_t>(op.numRecLast))) {
-        const ForeignBatchD b = op.batches[rid.batchID - op.baseBatchID];
-        if (b.isConst) {
-          r.bits = op.cbits;
-          r.ok = op.cok;
-          return r;
-        }
-        const uint32_t p = rid.index;
-        r = read_stored32(b.base + b.valuesOff, op.kind, op.step, p, p + b.bitOff);
-        r.ok = b.valuesOff != 0 ? get_bit(b.base + b.nullsOff, p + b.bitOff) : 1u;
-        if (op.tz) {  // enum -> utc offset (query/iterator.hpp:894-908)
-          DVal e = cvt32(r, op.kind, K_I32);
-          const int32_t ev = static_cast<int32_t>(e.bits);
-          DVal t;
-          t.ok = r.ok;
-          t.bits = ev < op.tzSize ? static_cast<uint32_t>(static_cast<int32_t>(op.tz[ev])) : 0u;
-          r = cvt32(t, K_I32, op.kind);
-        }
-      }
-      return r;
-    }
+    default:  // OP_FOREIGN
+      return load_foreign32(op, op.rids[i]);
   }
 }
 

@@ -1,4 +1,4 @@
-// AresFusedFilterSelect (include/ares_extensions.h): the non-aggregation query's batch — SELECT cols WHERE ... LIMIT n,
+// AresFusedFilterSelect and AresFusedFilterJoinSelect (include/ares_extensions.h): the non-aggregation query's batch — SELECT cols WHERE ... LIMIT n,
 // query/aql_nonaggr_batchexecutor.go — as ONE limit-aware pass over the source columns.
 //
 // The per-node sequence it replaces (InitIndexVector, a filter call per comparison, a transform call per dimension) reads
@@ -11,13 +11,19 @@
 // the grid is scanned whatever the batch size.  Values and validity bytes come from the functions the transform kernels
 // use (eval_quad, compare_tile, cvt32), so the bytes written equal the per-node sequence's for the same rows.
 //
-// Run-length (mode 3) columns — the sort columns of archive batches — are read where they lie (select_scan_kernel<true>): per
+// Run-length (mode 3) columns — the sort columns of archive batches — are read where they lie (select_scan_kernel<true, 0>): per
 // tile and column two scalar binary searches over the counts give the runs of the tile's first and last row.  One run: value
 // and validity are a broadcast, and a filter whose run is null or fails the comparison REJECTS the tile — its look-back word is
 // published with count 0 and no other column is read.  Several runs: the run ends inside the tile (at most 4095) are staged
 // in LDS, a lane searches them once per quad and walks the quad's other rows along them.  Plans without such a column run
-// select_scan_kernel<false>, the instruction sequence of before.  A GeoPoint column in the run-length layout is declined: the
+// select_scan_kernel<false, 0>, the instruction sequence of before.  A GeoPoint column in the run-length layout is declined: the
 // per-node sequence never decodes it (binding.hpp) and reads its rows past the run arrays.
+//
+// Joined columns (AresFusedFilterJoinSelect; select_scan_kernel<RUNS, 1 or 2>): the cuckoo probe of cuckoo_probe.hpp runs inside
+// the tile and the tile's record ids live in LDS (32 KiB per join).  A join that a foreign filter reads is probed before the
+// ranking, for the rows the main-table filters left alive; a join that only dimensions read is probed after the look-back, for
+// the rows that are written — a small limit costs that many probes.  Joined values are load_foreign32 (device_model.hpp), the
+// expressions over them the FastOperands of a column with validity.
 //
 // Stores go straight to the slots: the survivors of a wavefront's quads have consecutive ranks, so each store instruction
 // of a wavefront covers one contiguous byte range, and a quad that survives whole is stored as one 16 / 8 / 4 byte access.
@@ -252,6 +258,66 @@ __device__ __forceinline__ void store_wide_runs(const SelectDimD &D, const TileR
   }
 }
 
+// ---- joins ------------------------------------------------------------------------------------------------------------
+// The record ids of one join for the tile's rows live in LDS, row j of quad q of lane t at (q * kSelectBlock + t) * 4 + j: a
+// lane reads back what it wrote itself, so no barrier lies between the probe and the gathers.
+__device__ __forceinline__ int rid_slot(int q) { return (q * kSelectBlock + static_cast<int>(threadIdx.x)) * 4; }
+
+// rows of the quads with a local rank below `room`
+__device__ __forceinline__ void rows_below(const uint32_t (&alive)[Q], const uint32_t (&base)[Q], uint32_t room, uint32_t (&need)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    need[q] = 0;
+    uint32_t r = base[q];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      if (!((alive[q] >> j) & 1u)) continue;
+      if (r < room) need[q] |= 1u << j;
+      r++;
+    }
+  }
+}
+
+// Probes the index for the rows in `need`, one after the other (one copy of the probe in the code, and a lane walks only the
+// rows it has); a null key is a miss.  Returns the number of rows.  Starting a quad's four probes together — keys, then the
+// first signature words of all four, before any probe is finished — was measured and was no faster (profiles/r14_select_join.md).
+__device__ __forceinline__ uint32_t probe_rows(const SelectJoinD &J, int64_t row0, const uint32_t (&need)[Q], RecordID *sRid) {
+  const FastDivisor bucketDiv = make_fast_divisor(J.index.numBuckets);
+  uint32_t todo = 0;
+#pragma unroll
+  for (int q = 0; q < Q; q++) todo |= need[q] << (4 * q);
+  const uint32_t rows = __popc(todo);
+  while (todo) {
+    const int k = __builtin_ctz(todo);
+    todo &= todo - 1;
+    const int q = k >> 2, j = k & 3;
+    const uint32_t row = static_cast<uint32_t>(quad_row(row0, q)) + j;
+    uint32_t key[4] = {0, 0, 0, 0};
+    const uint32_t ok = cuckoo_load_key(J.key, row, row, nullptr, 0, key);
+    RecordID rid = {0, 0};
+    if (ok) rid = cuckoo_probe(J.index, bucketDiv, key);
+    sRid[rid_slot(q) + j] = rid;
+  }
+  return rows;
+}
+
+// load_column_tile for a joined column: the rows in `need` through their record ids; other rows read nothing (0, null)
+__device__ __forceinline__ void gather_tile(const OperandD &col, const RecordID *sRid, const uint32_t (&need)[Q], uint32_t (&vals)[Q][4], uint32_t (&okb)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; q++) {
+    okb[q] = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      vals[q][j] = 0;
+      if ((need[q] >> j) & 1u) {
+        const DVal v = load_foreign32(col, sRid[rid_slot(q) + j]);
+        vals[q][j] = v.bits;
+        okb[q] |= (v.ok ? 1u : 0u) << j;
+      }
+    }
+  }
+}
+
 struct ExprConst {
   DVal y;
   FastDivisor fd;
@@ -267,11 +333,15 @@ __device__ __forceinline__ ExprConst expr_const(const FastOperands &f) {  // as 
 }
 
 // A dimension of a 4 / 2 / 1 byte slot: the tile's survivors, ranks [base[q] ..) per quad, local ranks below `room` only.
-template <bool RUNS>
+// JOINED: a joined column — the values of the rows in *need (those that are written) through the record ids in sRid.
+template <bool RUNS, bool JOINED = false>
 __device__ __forceinline__ void store_narrow_dim(const SelectDimD &D, int64_t row0, int n, const uint32_t (&alive)[Q], const uint32_t (&base)[Q],
-                                                 uint32_t excl, uint32_t room, const TileRuns *t) {
+                                                 uint32_t excl, uint32_t room, const TileRuns *t, const OperandD *col = nullptr,
+                                                 const RecordID *sRid = nullptr, const uint32_t (*need)[Q] = nullptr) {
   uint32_t vals[Q][4], okb[Q];
-  if constexpr (RUNS) {
+  if constexpr (JOINED) {
+    gather_tile(*col, sRid, *need, vals, okb);
+  } else if constexpr (RUNS) {
     if (t) load_runs_tile(D.f, *t, vals, okb);
     else load_column_tile(D.f, row0, n, vals, okb);
   } else {
@@ -354,14 +424,28 @@ __device__ __forceinline__ void store_wide_dim(const SelectDimD &D, int64_t row0
 }
 
 
-// RUNS: the plan reads a mode-3 column.  <false> is the kernel of plans without one, instruction for instruction: three
-// workgroups per compute unit, 168 VGPRs, no scratch (a bound of four would spill).  <true> spills 11 VGPRs at three, so it is
-// bound to two and keeps everything in registers.
-template <bool RUNS>
-__global__ __launch_bounds__(kSelectBlock, RUNS ? 2 : 3) void select_scan_kernel(SelectPlanD p) {
+__device__ __forceinline__ const SelectJoinPlanD *join_plan() { return nullptr; }
+__device__ __forceinline__ const SelectJoinPlanD *join_plan(const SelectJoinPlanD &j) { return &j; }
+
+// RUNS: the plan reads a mode-3 column.  JOINS: the number of joins; 0 is the scan of AresFusedFilterSelect — one argument,
+// every join step compiled out — and 1 / 2 are the flavours of AresFusedFilterJoinSelect, with the joins' plan as the second
+// argument.
+// <false, 0> is the kernel of plans without a mode-3 column, instruction for instruction: three workgroups per compute unit,
+// 168 VGPRs, no scratch (a bound of four would spill).  <true, 0> spills 11 VGPRs at three, so it is bound to two and keeps
+// everything in registers.  The join flavours are bound to two as well: a tile's record ids take 32 KiB of LDS per join
+// (<true, 2>: 80 KiB with the run ends, one workgroup per compute unit, bound to one).
+template <bool RUNS, int JOINS, typename... JoinPlan>
+__global__ __launch_bounds__(kSelectBlock, JOINS == 0 ? (RUNS ? 2 : 3) : (RUNS && JOINS == 2) ? 1 : 2) void select_scan_kernel(SelectPlanD p, JoinPlan... j) {
+  [[maybe_unused]] const SelectJoinPlanD *jp = join_plan(j...);
   __shared__ uint64_t sWave[kSelectBlock / 64];
   __shared__ uint32_t sTileExcl;
   __shared__ int sTile;
+  RecordID *sRid = nullptr;
+  if constexpr (JOINS > 0) {
+    __shared__ RecordID rids[JOINS][kSelectTile];  // 32 KiB per join
+    sRid = &rids[0][0];
+  }
+  uint32_t probed = 0;  // (this lane's rows)
   uint32_t *sEnds = nullptr;
   if constexpr (RUNS) {
     __shared__ uint32_t ends[kSelectTile];  // one column's run ends inside the tile, column after column
@@ -453,6 +537,25 @@ __global__ __launch_bounds__(kSelectBlock, RUNS ? 2 : 3) void select_scan_kernel
       }
     }
 
+    // ---- joins that a foreign filter reads: probed for the survivors so far, then the filters over the joined values
+    if constexpr (JOINS > 0) {
+#pragma unroll
+      for (int k = 0; k < JOINS; k++)
+        if (jp->joins[k].early) probed += probe_rows(jp->joins[k], row0, alive, sRid + k * kSelectTile);
+      for (int k = 0; k < jp->numForeignFilters; k++) {
+        const FastOperands &f = jp->foreignFilters[k];
+        uint32_t vals[Q][4], okb[Q], kb[Q];
+        DVal y;
+        y.bits = f.bbits;
+        y.ok = f.bok;
+        y = cvt32(y, f.bkind, f.I);
+        gather_tile(jp->foreignFilterCols[k], sRid + jp->foreignFilterJoin[k] * kSelectTile, alive, vals, okb);
+        compare_tile<Q>(f, vals, okb, in, y, kb);
+#pragma unroll
+        for (int q = 0; q < Q; q++) alive[q] &= kb[q];
+      }
+    }
+
     // ---- ranks in row order: quad q of every lane precedes quad q + 1 of any lane — four counts scanned as one word
     uint64_t mine = 0;
 #pragma unroll
@@ -498,8 +601,21 @@ __global__ __launch_bounds__(kSelectBlock, RUNS ? 2 : 3) void select_scan_kernel
     // ---- the survivors' rows, ranks below the limit only
     if (tileCount > 0 && excl < p.limit) {
       const uint32_t room = p.limit - excl;
+      uint32_t need[Q];
+      if constexpr (JOINS > 0) {  // joins that only dimensions read: probed for the rows that are written
+        rows_below(alive, base, room, need);
+#pragma unroll
+        for (int k = 0; k < JOINS; k++)
+          if (!jp->joins[k].early) probed += probe_rows(jp->joins[k], row0, need, sRid + k * kSelectTile);
+      }
       for (int d = 0; d < p.numDims; d++) {
         const SelectDimD &D = p.dims[d];
+        if constexpr (JOINS > 0) {
+          if (jp->dimJoin[d] >= 0) {
+            store_narrow_dim<false, true>(D, row0, n, alive, base, excl, room, nullptr, &jp->dimCols[d], sRid + jp->dimJoin[d] * kSelectTile, &need);
+            continue;
+          }
+        }
         if constexpr (RUNS) {
           if (D.counts) {
             const TileRuns t = tile_runs(D.counts, D.runs, urow0, lastRow, sEnds, staged);
@@ -517,8 +633,21 @@ __global__ __launch_bounds__(kSelectBlock, RUNS ? 2 : 3) void select_scan_kernel
   }
 
   // ---- the last workgroup to leave publishes the result in the caller's pinned words
+  if constexpr (JOINS > 0) {  // the workgroup's probes, added once
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) probed += __shfl_down(probed, off);
+    __syncthreads();  // (sWave's readers of the last tile are through)
+    if (lane == 0) sWave[wave] = probed;
+    __syncthreads();
+  }
   if (threadIdx.x == 0) {
     if (scanned) atomicAdd(&p.state->scanned, scanned);
+    if constexpr (JOINS > 0) {
+      uint32_t all = 0;
+#pragma unroll
+      for (int w = 0; w < kSelectBlock / 64; w++) all += static_cast<uint32_t>(sWave[w]);
+      if (all) atomicAdd(&p.state->probed, all);
+    }
     if constexpr (RUNS) {
       if (rejectedTiles) atomicAdd(&p.state->rejected, rejectedTiles);
       if (stagedTiles) atomicAdd(&p.state->staged, stagedTiles);
@@ -534,6 +663,7 @@ __global__ __launch_bounds__(kSelectBlock, RUNS ? 2 : 3) void select_scan_kernel
         p.result[3] = ld_word(&p.state->rejected);
         p.result[4] = ld_word(&p.state->staged);
       }
+      if constexpr (JOINS > 0) p.result[5] = ld_word(&p.state->probed);
     }
   }
 }
@@ -545,33 +675,41 @@ struct NotFusable : std::runtime_error {
 
 std::atomic<unsigned long long> g_stats[4];     // batches run, batches declined, tiles scanned, rows written
 std::atomic<unsigned long long> g_runStats[2];  // tiles rejected by a run, tiles that staged run ends
+std::atomic<unsigned long long> g_joinStats[5];  // AresFusedFilterJoinSelect: batches run, declined, tiles scanned, rows written, keys probed
 
 bool select_enabled() {
   static EnvSwitch<bool> on("ARES_SELECT", [](const char *e) { return !(e && e[0] == '0'); });
   return on.get();
 }
 
+// the kernel of a plan: RUNS x number of joins
+const void *select_kernel(bool runs, int joins) {
+  if (joins == 0) return runs ? reinterpret_cast<const void *>(&select_scan_kernel<true, 0>) : reinterpret_cast<const void *>(&select_scan_kernel<false, 0>);
+  if (joins == 1) return runs ? reinterpret_cast<const void *>(&select_scan_kernel<true, 1, SelectJoinPlanD>) : reinterpret_cast<const void *>(&select_scan_kernel<false, 1, SelectJoinPlanD>);
+  return runs ? reinterpret_cast<const void *>(&select_scan_kernel<true, 2, SelectJoinPlanD>) : reinterpret_cast<const void *>(&select_scan_kernel<false, 2, SelectJoinPlanD>);
+}
+
 // workgroups of one launch: as many as the device holds at once; ARES_SELECT_GRID=n (tests) overrides
-int select_grid(int device, bool runs) {
+int select_grid(int device, bool runs, int joins) {
   static EnvSwitch<int> forced("ARES_SELECT_GRID", [](const char *e) { return e ? atoi(e) : 0; });
   const int f = forced.get();
   if (f > 0) return std::min(f, kSelectGridCap);
   static std::mutex mu;
-  static std::map<std::pair<int, bool>, int> known;
+  static std::map<std::pair<int, const void *>, int> known;
   std::lock_guard<std::mutex> lock(mu);
-  auto it = known.find({device, runs});
+  const void *kernel = select_kernel(runs, joins);
+  auto it = known.find({device, kernel});
   if (it != known.end()) return it->second;
   int perCU = 0, cus = 0;
-  const void *kernel = runs ? reinterpret_cast<const void *>(&select_scan_kernel<true>) : reinterpret_cast<const void *>(&select_scan_kernel<false>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kernel, kSelectBlock, 0) != hipSuccess || perCU < 1) {
     (void)hipGetLastError();
-    perCU = 4;
+    perCU = joins ? 1 : 4;
   }
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus < 1) {
     (void)hipGetLastError();
     cus = 256;
   }
-  return known[{device, runs}] = std::max(1, std::min(perCU * cus, kSelectGridCap));
+  return known[{device, kernel}] = std::max(1, std::min(perCU * cus, kSelectGridCap));
 }
 
 bool wide_type(int t) { return t == Int64 || t == Uint64 || t == GeoPoint || t == UUID; }
@@ -595,6 +733,17 @@ void check_column(const AresFusedExpr &e, int batchRows) {
   if (static_cast<int64_t>(vp.Length) < batchRows) throw NotFusable("column shorter than the batch");
 }
 
+// a joined column of a foreign filter or a joined dimension
+void check_foreign_column(const AresFusedExpr &e) {
+  if (e.arity != 1 && e.arity != 2) throw NotFusable("arity");
+  if (e.lhs.Type != ForeignColumnInput || (e.arity == 2 && e.rhs.Type != ConstantInput))
+    throw NotFusable("operands must be a joined column and a constant");
+  const ForeignColumnVector &f = e.lhs.Vector.ForeignVP;
+  if (f.DataType == Bool || wide_type(f.DataType)) throw NotFusable("Bool or wide joined column");
+  if (f.TimezoneLookup) throw NotFusable("timezone lookup");
+  if (f.NumBatches < 0 || (f.NumBatches > 0 && !f.Batches)) throw NotFusable("joined column without batches");
+}
+
 // the run description of a bound mode-3 column
 struct RunsOf {
   const uint32_t *counts = nullptr;
@@ -602,18 +751,31 @@ struct RunsOf {
 };
 
 // a filter, or a dimension of a 4 / 2 / 1 byte slot: the operand shape of the fast transform / filter kernels
-FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream, RunsOf &runs) {
-  check_column(e, batchRows);
-  if (wide_type(e.lhs.Vector.VP.DataType)) throw NotFusable("expression over a wide column");
+// `foreign` (join flavour): the expression's column is a joined one — bound into *foreign as an OP_FOREIGN operand, its batch
+// descriptors uploaded on the stream and kept in `temps`; the FastOperands are those of a column with validity.
+FastOperands narrow_operands(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream, RunsOf &runs, CallTemps &temps,
+                             OperandD *foreign = nullptr) {
+  if (foreign) check_foreign_column(e);
+  else check_column(e, batchRows);
+  if (!foreign && wide_type(e.lhs.Vector.VP.DataType)) throw NotFusable("expression over a wide column");
   InputVector ins[2] = {e.lhs, e.arity == 2 ? e.rhs : e.lhs};
   EvalParams p;
-  CallTemps temps;
   try {
     build_params(ins, e.arity, stream, nullptr, nullptr, 0, e.functor, p, temps);
   } catch (const std::invalid_argument &bad) {
     throw NotFusable(bad.what());
   }
   runs = RunsOf();
+  if (foreign) {
+    if (p.a.type != OP_FOREIGN) throw NotFusable("joined column");
+    *foreign = p.a;
+    foreign->rids = nullptr;  // (the tile's record ids are the kernel's own)
+    p.a.type = OP_COLUMN;
+    p.a.mode = 2;
+    p.a.base = nullptr;
+    p.a.nullsOff = p.a.valuesOff = 0;
+    p.a.bitOff = 0;
+  }
   if (p.a.type == OP_COLUMN && p.a.mode == 3) {
     // Bound here, not by the deferral machinery's fast_operands(): the expression shapes are the ones it takes for a column
     // with validity (same kinds, widths and functors), and vals / nulls name the RUN arrays
@@ -659,45 +821,92 @@ FastOperands wide_operands(const AresFusedExpr &e, int batchRows, hipStream_t st
   return f;
 }
 
-int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int limit, const DimensionVector &outKeys, hipStream_t stream) {
+// a join's key column and index: the conditions and messages of HashLookup
+SelectJoinD bind_join(const AresFusedJoin &j, int batchRows, hipStream_t stream, CallTemps &temps) {
+  if (j.key.Type != VectorPartyInput) throw NotFusable("the join key must be a main-table column");
+  const VectorPartySlice &vp = j.key.Vector.VP;
+  if (!vp.BasePtr) throw NotFusable("mode 0 join key");
+  if (run_length_layout(vp)) throw NotFusable("run-length join key");
+  if (static_cast<int64_t>(vp.Length) < batchRows) throw NotFusable("column shorter than the batch");
+  SelectJoinD J;
+  memset(&J, 0, sizeof(J));
+  try {
+    bind_operand(j.key, true, stream, J.key, temps);
+  } catch (const std::invalid_argument &bad) {
+    throw NotFusable(bad.what());
+  }
+  if (J.key.kind == K_GEO) throw NotFusable("Unsupported data type for HashLookup");
+  if (!cuckoo_geometry_ok(j.index) || !j.index.buckets) throw NotFusable("Unsupported cuckoo hash index geometry");
+  J.index = make_cuckoo(j.index);
+  return J;
+}
+
+// The select scan of one batch; `jq` (may be null): the joins, foreign filters and the joined dimensions of
+// AresFusedFilterJoinSelect — filters / dims are then its main-table filters and all its dimensions.
+int fused_select(int device, int numFilters, const AresFusedExpr *filters, int numDims, const AresFusedExpr *dims, const AresFusedJoinSelect *jq,
+                 int batchRows, int limit, const DimensionVector &outKeys, hipStream_t stream) {
   if (!select_enabled()) throw NotFusable("switched off (ARES_SELECT=0)");
-  if (q.numFilters < 0 || q.numFilters > kSelectFilters) throw NotFusable("at most 4 filters");
-  if (q.numDims < 1 || q.numDims > kSelectDims) throw NotFusable("1..8 dimensions");
+  if (numFilters < 0 || numFilters > kSelectFilters) throw NotFusable("at most 4 filters");
+  if (numDims < 1 || numDims > kSelectDims) throw NotFusable("1..8 dimensions");
   if (batchRows < 0) throw NotFusable("size");
+  if (jq) {
+    if (jq->numJoins < 1 || jq->numJoins > kSelectJoins) throw NotFusable("1..2 joins (none: AresFusedFilterSelect)");
+    if (jq->numForeignFilters < 0 || jq->numForeignFilters > kSelectForeignFilters) throw NotFusable("at most 4 foreign filters");
+  }
   DimLayoutD L;
   try {
     L = make_dim_layout(outKeys.NumDimsPerDimWidth);
   } catch (const std::invalid_argument &) {
     throw NotFusable("dimension vector layout");
   }
-  if (L.numDims != q.numDims) throw NotFusable("dimension vector layout");
+  if (L.numDims != numDims) throw NotFusable("dimension vector layout");
 
+  CallTemps temps;  // (the joined columns' batch descriptors: alive until the launch has finished)
   SelectPlanD plan;
   memset(&plan, 0, sizeof(plan));
-  plan.numFilters = q.numFilters;
-  plan.numDims = q.numDims;
+  SelectJoinPlanD joins;
+  memset(&joins, 0, sizeof(joins));
+  for (int d = 0; d < kSelectDims; d++) joins.dimJoin[d] = -1;
+  plan.numFilters = numFilters;
+  plan.numDims = numDims;
   bool anyRuns = false;
   RunsOf runs;
-  for (int k = 0; k < q.numFilters; k++) {
-    plan.filters[k] = narrow_operands(q.filters[k], true, batchRows, stream, runs);
+  for (int k = 0; k < numFilters; k++) {
+    plan.filters[k] = narrow_operands(filters[k], true, batchRows, stream, runs, temps);
     plan.filterCounts[k] = runs.counts;
     plan.filterRuns[k] = runs.runs;
     anyRuns |= runs.counts != nullptr;
   }
+  if (jq) {
+    joins.numJoins = jq->numJoins;
+    joins.numForeignFilters = jq->numForeignFilters;
+    for (int k = 0; k < jq->numJoins; k++) joins.joins[k] = bind_join(jq->joins[k], batchRows, stream, temps);
+    for (int k = 0; k < jq->numForeignFilters; k++) {
+      const int j = jq->foreignFilterJoin[k];
+      if (j < 0 || j >= jq->numJoins) throw NotFusable("join index out of range");
+      joins.foreignFilters[k] = narrow_operands(jq->foreignFilters[k], true, batchRows, stream, runs, temps, &joins.foreignFilterCols[k]);
+      joins.foreignFilterJoin[k] = j;
+      joins.joins[j].early = 1;
+    }
+  }
   const size_t capacity = static_cast<size_t>(outKeys.VectorCapacity > 0 ? outKeys.VectorCapacity : 0);
-  for (int d = 0; d < q.numDims; d++) {
-    const int t = q.dims[d].outType;
+  for (int d = 0; d < numDims; d++) {
+    const int t = dims[d].outType;
     const bool narrow = t == Int8 || t == Uint8 || t == Int16 || t == Uint16 || t == Int32 || t == Uint32 || t == Float32;
     if (!narrow && !(t == Int64 || t == GeoPoint || t == UUID)) throw NotFusable("dimension type");
+    const int dimJoin = jq ? jq->dimJoin[d] : -1;
+    if (dimJoin >= (jq ? jq->numJoins : 0)) throw NotFusable("join index out of range");
+    joins.dimJoin[d] = dimJoin < 0 ? -1 : dimJoin;
     SelectDimD &D = plan.dims[d];
     D.width = step_in_bytes(t);
     if (D.width != L.width[d]) throw NotFusable("dimension vector layout");
+    if (dimJoin >= 0 && !narrow) throw NotFusable("Bool or wide joined column");
     if (narrow) {
-      D.f = narrow_operands(q.dims[d], false, batchRows, stream, runs);
+      D.f = narrow_operands(dims[d], false, batchRows, stream, runs, temps, dimJoin >= 0 ? &joins.dimCols[d] : nullptr);
       if (D.width < 4 && !(D.f.rk == K_I32 || D.f.rk == K_U32)) throw NotFusable("float result into a narrow slot");
       D.outKind = t == Int32 ? K_I32 : t == Uint32 ? K_U32 : K_F32;
     } else {
-      D.f = wide_operands(q.dims[d], batchRows, stream, runs);
+      D.f = wide_operands(dims[d], batchRows, stream, runs);
     }
     D.counts = runs.counts;
     D.runs = runs.runs;
@@ -711,15 +920,16 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
   if (wanted == 0) return 0;
 
   // a 4-byte column that the plan reads once is loaded non-temporally (modes 1/2: the run arrays of a mode-3 column are
-  // small and read again and again)
+  // small and read again and again; a joined column is gathered)
   auto uses = [&](const uint32_t *vals) {
     int c = 0;
     for (int k = 0; k < plan.numFilters; k++) c += plan.filters[k].vals == vals;
     for (int d = 0; d < plan.numDims; d++) c += plan.dims[d].f.vals == vals;
+    for (int k = 0; k < joins.numJoins; k++) c += reinterpret_cast<const uint32_t *>(joins.joins[k].key.base + joins.joins[k].key.valuesOff) == vals;
     return c;
   };
   for (int k = 0; k < plan.numFilters; k++) plan.filters[k].streaming = !plan.filterCounts[k] && uses(plan.filters[k].vals) == 1;
-  for (int d = 0; d < plan.numDims; d++) plan.dims[d].f.streaming = !plan.dims[d].counts && uses(plan.dims[d].f.vals) == 1;
+  for (int d = 0; d < plan.numDims; d++) plan.dims[d].f.streaming = joins.dimJoin[d] < 0 && !plan.dims[d].counts && uses(plan.dims[d].f.vals) == 1;
 
   flush_deferred_for_vector(device, outKeys, nullptr, 0);
   grouped_note_write(device, outKeys);
@@ -736,18 +946,29 @@ int fused_filter_select(int device, const AresFusedSelect &q, int batchRows, int
   plan.result = const_cast<uint32_t *>(result);
   result[0] = 0u;
   result[1] = 2u;  // (overwritten by the launch's last workgroup)
-  result[2] = result[3] = result[4] = 0u;
-  const int grid = std::min(select_grid(device, anyRuns), plan.numTiles);
-  if (anyRuns) ARES_LAUNCH("select_scan_kernel", (select_scan_kernel<true>), grid, kSelectBlock, stream, plan);
-  else ARES_LAUNCH("select_scan_kernel", (select_scan_kernel<false>), grid, kSelectBlock, stream, plan);
+  result[2] = result[3] = result[4] = result[5] = 0u;
+  const int grid = std::min(select_grid(device, anyRuns, joins.numJoins), plan.numTiles);
+  if (joins.numJoins == 2) {
+    if (anyRuns) ARES_LAUNCH("select_join_kernel", (select_scan_kernel<true, 2, SelectJoinPlanD>), grid, kSelectBlock, stream, plan, joins);
+    else ARES_LAUNCH("select_join_kernel", (select_scan_kernel<false, 2, SelectJoinPlanD>), grid, kSelectBlock, stream, plan, joins);
+  } else if (joins.numJoins == 1) {
+    if (anyRuns) ARES_LAUNCH("select_join_kernel", (select_scan_kernel<true, 1, SelectJoinPlanD>), grid, kSelectBlock, stream, plan, joins);
+    else ARES_LAUNCH("select_join_kernel", (select_scan_kernel<false, 1, SelectJoinPlanD>), grid, kSelectBlock, stream, plan, joins);
+  } else if (anyRuns) {
+    ARES_LAUNCH("select_scan_kernel", (select_scan_kernel<true, 0>), grid, kSelectBlock, stream, plan);
+  } else {
+    ARES_LAUNCH("select_scan_kernel", (select_scan_kernel<false, 0>), grid, kSelectBlock, stream, plan);
+  }
   hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
   ws.mark_idle();
   if (result[1] == 2u) throw AlgorithmError("ERROR: select scan: the launch finished without publishing its result");
   if (result[1] != 0u) throw AlgorithmError("ERROR: select scan: a look-back wait gave up");
   const uint32_t rows = result[0];
-  g_stats[0]++;
-  g_stats[2] += result[2];
-  g_stats[3] += rows;
+  std::atomic<unsigned long long> *stats = jq ? g_joinStats : g_stats;
+  stats[0]++;
+  stats[2] += result[2];
+  stats[3] += rows;
+  if (jq) stats[4] += result[5];
   g_runStats[0] += result[3];
   g_runStats[1] += result[4];
   mem_note_dim_rows(device, outKeys, 0, rows);
@@ -763,7 +984,8 @@ extern "C" CGoCallResHandle AresFusedFilterSelect(const AresFusedSelect *query, 
   ARES_ABI_BEGIN(device)
   if (!query) throw std::invalid_argument("null query");
   try {
-    resHandle.res = ares::int_result(ares::fused_filter_select(device, *query, batchRows, limit, outKeys, reinterpret_cast<hipStream_t>(cudaStream)));
+    resHandle.res = ares::int_result(ares::fused_select(device, query->numFilters, query->filters, query->numDims, query->dims, nullptr, batchRows, limit,
+                                                        outKeys, reinterpret_cast<hipStream_t>(cudaStream)));
   } catch (const ares::NotFusable &) {
     ares::g_stats[1]++;
     throw;
@@ -779,4 +1001,23 @@ extern "C" void AresSelectStats(unsigned long long *counters) {
 extern "C" void AresSelectRunStats(unsigned long long *counters) {
   if (!counters) return;
   for (int i = 0; i < 2; i++) counters[i] = ares::g_runStats[i].load();
+}
+
+extern "C" CGoCallResHandle AresFusedFilterJoinSelect(const AresFusedJoinSelect *query, int batchRows, int limit, DimensionVector outKeys,
+                                                      void *cudaStream, int device) {
+  ARES_ABI_BEGIN(device)
+  if (!query) throw std::invalid_argument("null query");
+  try {
+    resHandle.res = ares::int_result(ares::fused_select(device, query->numFilters, query->filters, query->numDims, query->dims, query, batchRows, limit,
+                                                        outKeys, reinterpret_cast<hipStream_t>(cudaStream)));
+  } catch (const ares::NotFusable &) {
+    ares::g_joinStats[1]++;
+    throw;
+  }
+  ARES_ABI_END("AresFusedFilterJoinSelect")
+}
+
+extern "C" void AresSelectJoinStats(unsigned long long *counters) {
+  if (!counters) return;
+  for (int i = 0; i < 5; i++) counters[i] = ares::g_joinStats[i].load();
 }

@@ -6,6 +6,8 @@
 
 #include <cstdint>
 
+#include "cuckoo_probe.hpp"
+#include "device_model.hpp"
 #include "fast_eval.hpp"
 
 namespace ares {
@@ -16,6 +18,8 @@ constexpr int kSelectBlock = 256;
 constexpr int kSelectQuads = 4;                                   // quads per lane and tile
 constexpr int kSelectTile = kSelectBlock * 4 * kSelectQuads;      // 4096 rows
 constexpr int kSelectGridCap = 2048;
+constexpr int kSelectJoins = 2;           // AresFusedJoinSelect::joins
+constexpr int kSelectForeignFilters = 4;  // AresFusedJoinSelect::foreignFilters
 
 // One dimension of the plan.  width 4 / 2 / 1: `f` is the expression (column pointers included) and the slot receives what
 // the transform kernels store for it; width 8 / 16: a bare column, f.vals / f.nulls / f.bitOff name it and the slot receives
@@ -42,8 +46,10 @@ struct SelectStateD {
   uint32_t scanned;  // tiles whose columns were read
   uint32_t rejected;  // of those: thrown away by ONE run of a mode-3 filter column that is null or fails the comparison
   uint32_t staged;    // of those: tiles that staged the run ends of some mode-3 column in LDS (several runs in the tile)
+  uint32_t probed;    // join flavours: rows whose key went to the cuckoo probe
+  uint32_t pad;
 };
-static_assert(sizeof(SelectStateD) == 32, "the state block is cleared as a whole and the status words follow it");
+static_assert(sizeof(SelectStateD) == 40, "the state block is cleared as a whole and the status words follow it");
 
 struct SelectPlanD {
   int numFilters, numDims;
@@ -55,7 +61,29 @@ struct SelectPlanD {
   uint32_t limit;  // 0xFFFFFFFF: none
   SelectStateD *state;
   uint64_t *status;   // one look-back word per tile
-  uint32_t *result;   // mapped pinned words of the calling thread: {rows, error, tiles scanned, rejected, staged}
+  uint32_t *result;   // mapped pinned words of the calling thread: {rows, error, tiles scanned, rejected, staged, keys probed}
 };
+
+// The joins of a plan (AresFusedFilterJoinSelect): the second argument of the join flavours of the kernel.  A joined column is
+// an OP_FOREIGN operand without record ids — the tile's record ids are staged in LDS by the probe — and its expression is the
+// FastOperands of a column with validity (vals / nulls unused): foreignFilters[k] here, SelectDimD::f for a dimension.
+struct SelectJoinD {
+  OperandD key;    // the main-table key column, modes 1/2
+  CuckooD index;
+  int early;       // some foreign filter reads the join: probed before ranking, for the survivors of the main-table filters;
+  int pad;         // otherwise after the look-back, for the rows that are written
+};
+
+struct SelectJoinPlanD {
+  int numJoins, numForeignFilters;
+  SelectJoinD joins[kSelectJoins];
+  FastOperands foreignFilters[kSelectForeignFilters];
+  OperandD foreignFilterCols[kSelectForeignFilters];
+  int foreignFilterJoin[kSelectForeignFilters];
+  OperandD dimCols[kSelectDims];  // of dimensions with dimJoin[d] >= 0
+  int dimJoin[kSelectDims];       // -1: a main-table dimension
+};
+
+static_assert(sizeof(SelectPlanD) + sizeof(SelectJoinPlanD) <= 4096, "the two plans are the kernel's arguments");
 
 }  // namespace ares

@@ -59,6 +59,7 @@ struct AbiLibrary {
   decltype(&::HashReduce) HashReduce;
   decltype(&::AresFusedFilterHashReduce) FusedFilterHashReduce = nullptr;  // optional extension
   decltype(&::AresFusedFilterSelect) FusedFilterSelect = nullptr;          // optional extension
+  decltype(&::AresFusedFilterJoinSelect) FusedFilterJoinSelect = nullptr;  // optional extension
   decltype(&::Expand) Expand;
   // libmem
   decltype(&::DeviceAllocate) DeviceAllocate;
@@ -109,6 +110,7 @@ struct AbiLibrary {
     bind(algoHandle, "Expand", Expand);
     FusedFilterHashReduce = reinterpret_cast<decltype(FusedFilterHashReduce)>(dlsym(algoHandle, "AresFusedFilterHashReduce"));
     FusedFilterSelect = reinterpret_cast<decltype(FusedFilterSelect)>(dlsym(algoHandle, "AresFusedFilterSelect"));
+    FusedFilterJoinSelect = reinterpret_cast<decltype(FusedFilterJoinSelect)>(dlsym(algoHandle, "AresFusedFilterJoinSelect"));
     bind(memHandle, "DeviceAllocate", DeviceAllocate);
     bind(memHandle, "DeviceFree", DeviceFree);
     bind(memHandle, "WaitForCudaStream", WaitForCudaStream);
@@ -400,7 +402,8 @@ struct AresQuery {
   // -- processExpression (time_series_aggregate.go:491-593) --
   std::vector<std::vector<VectorPartySlice>> foreignSliceArrays;  // Go slices handed to the callee for one call
 
-  IV columnInput(const AresPlanNode &n) {
+  // withRids = false: a joined column for AresFusedFilterJoinSelect, which has no record-id vectors
+  IV columnInput(const AresPlanNode &n, bool withRids = true) {
     IV iv;
     if (n.table == 0) {
       if (n.column < 0 || n.column >= numColumns) throw AbiError("column index out of range");
@@ -412,7 +415,7 @@ struct AresQuery {
     foreignSliceArrays.emplace_back(ft.slices.begin() + static_cast<size_t>(n.column) * ft.t.numBatches,
                                     ft.slices.begin() + static_cast<size_t>(n.column + 1) * ft.t.numBatches);
     ForeignColumnVector &f = iv->Vector.ForeignVP;
-    f.RecordIDs = foreignRids.at(n.table - 1);
+    f.RecordIDs = withRids ? foreignRids.at(n.table - 1) : nullptr;
     f.Batches = foreignSliceArrays.back().data();
     f.BaseBatchID = ft.t.baseBatchID;
     f.NumBatches = ft.t.numBatches;
@@ -781,13 +784,16 @@ struct AresQuery {
   }
 
   // ---- fused extension (include/ares_extensions.h): one call per batch --------------------------
-  bool fusedExpr(int nodeIdx, int outType, AresFusedExpr *e) {
+  // *join (may be null: main-table columns only) receives the leaf column's join, table - 1, or -1 for the main table
+  bool fusedExpr(int nodeIdx, int outType, AresFusedExpr *e, int *join = nullptr) {
     const AresPlanNode &n = plan.nodes.at(nodeIdx);
     memset(e, 0, sizeof(*e));
     e->outType = static_cast<DataType>(outType);
     auto leafColumn = [&](const AresPlanNode &c, InputVector *iv) {
-      if (c.kind != ARES_NODE_COLUMN || c.table != 0) return false;
-      memcpy(iv, &columnInput(c).get(), sizeof(InputVector));
+      if (c.kind != ARES_NODE_COLUMN || c.table < 0 || c.table > static_cast<int>(plan.foreign.size())) return false;
+      if (c.table != 0 && !join) return false;
+      if (join) *join = c.table - 1;
+      memcpy(iv, &columnInput(c, false).get(), sizeof(InputVector));
       return true;
     };
     if (n.kind == ARES_NODE_COLUMN) {
@@ -845,26 +851,57 @@ struct AresQuery {
     return true;
   }
 
-  // The non-aggregation batch through AresFusedFilterSelect (include/ares_extensions.h): filters and dimensions of a batch
-  // without base counts, joins or geo in one limit-aware call.  false: this batch takes the ordinary sequence.
+  // The non-aggregation batch through AresFusedFilterSelect or, for a plan with foreign tables, AresFusedFilterJoinSelect
+  // (include/ares_extensions.h): filters, joins, foreign filters and dimensions of a batch without base counts or geo in one
+  // limit-aware call; no record-id vectors are allocated.  false: this batch takes the ordinary sequence.
   bool runBatchFusedSelect(const VectorPartySlice *cols, int ncols, int n) {
-    if (!plan.useFusedExtension || fusedDeclined || !lib->FusedFilterSelect) return false;
-    if (baseCounts || plan.hasGeo || !plan.foreign.empty() || !plan.foreignFilters.empty()) return false;
+    const bool joins = !plan.foreign.empty() || !plan.foreignFilters.empty();
+    if (!plan.useFusedExtension || fusedDeclined || !(joins ? lib->FusedFilterJoinSelect != nullptr : lib->FusedFilterSelect != nullptr)) return false;
+    if (baseCounts || plan.hasGeo) return false;
+    if (plan.foreign.size() > 2 || plan.foreignFilters.size() > 4) return false;
     if (plan.dimNodes.empty() || plan.dimNodes.size() > 8 || plan.filters.size() > 4) return false;
     columns = cols;
     numColumns = ncols;
-    Pod<AresFusedSelect> q;
-    q->numFilters = static_cast<int>(plan.filters.size());
-    for (size_t i = 0; i < plan.filters.size(); i++)
-      if (!fusedExpr(plan.filters[i], Bool, &q->filters[i])) return false;
-    q->numDims = static_cast<int>(plan.dimNodes.size());
-    for (size_t i = 0; i < plan.dimNodes.size(); i++)
-      if (!fusedExpr(plan.dimNodes[i], plan.dimTypes[i], &q->dims[dimVectorIndex[i]])) return false;
-    size = n;
-    batchRows = n;
-    prepareForDimEval();
-    calls++;
-    CGoCallResHandle h = lib->FusedFilterSelect(&q.get(), n, recordsNeeded(), dimensionVector(0), stream, device);
+    CGoCallResHandle h;
+    if (joins) {
+      Pod<AresFusedJoinSelect> q;
+      q->numFilters = static_cast<int>(plan.filters.size());
+      for (size_t i = 0; i < plan.filters.size(); i++)
+        if (!fusedExpr(plan.filters[i], Bool, &q->filters[i])) return false;
+      q->numJoins = static_cast<int>(plan.foreign.size());
+      for (size_t k = 0; k < plan.foreign.size(); k++) {
+        AresPlanNode key;
+        memset(&key, 0, sizeof(key));
+        key.kind = ARES_NODE_COLUMN;
+        key.column = plan.foreign[k].t.joinColumn;
+        memcpy(&q->joins[k].key, &columnInput(key).get(), sizeof(InputVector));
+        memcpy(&q->joins[k].index, &plan.foreign[k].t.index, sizeof(CuckooHashIndex));
+      }
+      q->numForeignFilters = static_cast<int>(plan.foreignFilters.size());
+      for (size_t i = 0; i < plan.foreignFilters.size(); i++)
+        if (!fusedExpr(plan.foreignFilters[i], Bool, &q->foreignFilters[i], &q->foreignFilterJoin[i]) || q->foreignFilterJoin[i] < 0) return false;
+      q->numDims = static_cast<int>(plan.dimNodes.size());
+      for (size_t i = 0; i < plan.dimNodes.size(); i++)
+        if (!fusedExpr(plan.dimNodes[i], plan.dimTypes[i], &q->dims[dimVectorIndex[i]], &q->dimJoin[dimVectorIndex[i]])) return false;
+      size = n;
+      batchRows = n;
+      prepareForDimEval();
+      calls++;
+      h = lib->FusedFilterJoinSelect(&q.get(), n, recordsNeeded(), dimensionVector(0), stream, device);
+    } else {
+      Pod<AresFusedSelect> q;
+      q->numFilters = static_cast<int>(plan.filters.size());
+      for (size_t i = 0; i < plan.filters.size(); i++)
+        if (!fusedExpr(plan.filters[i], Bool, &q->filters[i])) return false;
+      q->numDims = static_cast<int>(plan.dimNodes.size());
+      for (size_t i = 0; i < plan.dimNodes.size(); i++)
+        if (!fusedExpr(plan.dimNodes[i], plan.dimTypes[i], &q->dims[dimVectorIndex[i]])) return false;
+      size = n;
+      batchRows = n;
+      prepareForDimEval();
+      calls++;
+      h = lib->FusedFilterSelect(&q.get(), n, recordsNeeded(), dimensionVector(0), stream, device);
+    }
     if (h.pStrErr && strncmp(h.pStrErr, "not fusable", 11) == 0) {
       free(const_cast<char *>(h.pStrErr));
       fusedDeclined = true;  // (as runBatchFused: the plan's shape does not change, stop asking)

@@ -75,8 +75,10 @@ typedef struct {
    * literal, query/aql_compiler.go:1147-1153) runs as query/aql_nonaggr_batchexecutor.go does: filters and joins, the
    * dimensions written from row 0, Expand when the batch has base counts, the rows cut to what is still wanted, no
    * measure and no reduction, the batch's rows copied to the host, and the query is DONE once `limit` rows exist
-   * (limit < 0: none).  With useFusedExtension a batch without base counts, joins or geo is tried through
-   * AresFusedFilterSelect first; once the library has declined the plan ("not fusable") the query stops asking.  Both 0: an aggregation query, as before. */
+   * (limit < 0: none).  With useFusedExtension a batch without base counts or geo is tried through AresFusedFilterSelect
+   * first — a plan with foreign tables (at most two, at most four foreign filters) through AresFusedFilterJoinSelect, without
+   * record-id vectors; once the library has declined the plan ("not fusable") the query stops asking.  Both 0: an aggregation
+   * query, as before. */
   int isNonAggregation;
   int limit;
 } AresQueryPlan;

@@ -201,7 +201,8 @@ CGoCallResHandle AresFusedFilterHashReduce(const AresFusedQuery *query, int batc
  * holds for archive batches too, and a tile that lies inside ONE run of a filter column that is null or fails the comparison
  * is thrown away without reading any other column (AresSelectRunStats counts them).
  * Declined: Bool and Uint64 columns, mode 0 columns, a GeoPoint column in the mode-3 layout (the per-node sequence never
- * decodes one: it reads it row by row as a mode-2 column), a mode-3 column without runs, foreign-table and array operands,
+ * decodes one: it reads it row by row as a mode-2 column), a mode-3 column without runs, foreign-table operands (those go to
+ * AresFusedFilterJoinSelect below) and array operands,
  * expressions over a wide column.  outKeys.VectorCapacity must be at least batchRows (limit < 0) or
  * min(batchRows, limit); batchRows == 0 or limit == 0 returns 0 and launches nothing.
  * Environment (both obey AresReloadEnv): ARES_SELECT=0 declines always; ARES_SELECT_GRID=n (tests) sets the number of
@@ -220,6 +221,57 @@ void AresSelectStats(unsigned long long *counters);
 /* {tiles rejected by one run of a run-length filter column, tiles that staged run ends in LDS} since process start; both are
  * counted among the tiles scanned */
 void AresSelectRunStats(unsigned long long *counters);
+
+/* Fused select scan with joins: the batch of a non-aggregation query that selects or filters on columns of joined dimension
+ * tables, with the cuckoo probe inside the scan.  For one batch without base counts it replaces the call sequence
+ *   InitIndexVector, BinaryFilter x numFilters, HashLookup x numJoins over the survivors (baseCounts NULL, startCount 0),
+ *   BinaryFilter x numForeignFilters (the record-id vectors of all joins carried along),
+ *   Unary/BinaryTransform x numDims into rows [0, survivors) of outKeys
+ * cut at `limit` exactly as AresFusedFilterSelect is: rows [0, res) of outKeys hold, byte for byte, what the sequence stores
+ * for the first min(survivors, limit) survivors in ascending row order (value bytes of null rows included), nothing at or
+ * beyond res is written, res = that count.
+ * An expression with foreignFilterJoin[k] / dimJoin[d] >= 0 has a ForeignColumnInput as lhs: Batches, BaseBatchID, NumBatches,
+ * NumRecordsInLastBatch, DataType and DefaultValue mean what they mean for UnaryTransform; RecordIDs is ignored — no record-id
+ * vector exists on this path.  A joined value is what the per-node sequence reads: a missing or null key, a batchID outside
+ * the table and an index at or past NumRecordsInLastBatch in the last batch give value bits 0 and validity 0; a mode-0 batch
+ * gives the default value and the default's validity; a batch with ValuesOffset != 0 takes validity from its bitmap; any other
+ * batch is valid.  A foreign filter treats a null operand as the main-table filters do.
+ * A join that some foreign filter reads is probed, per 4096-row tile, for the rows the main-table filters left alive; a join
+ * that only dimensions read is probed for the rows that are written — with a small limit, that many keys and no more.  The
+ * tile-level early out of AresFusedFilterSelect applies unchanged.
+ *
+ * Shapes accepted: main-table filters and dimensions as AresFusedFilterSelect (run-length columns included); 1-2 joins, the
+ * key a bare main-table column in mode 1 or 2 of any type and index geometry HashLookup accepts for one (1-, 2- and 4-byte
+ * types, Int64, UUID; keyBytes 1..16, numHashes 0..4, numBuckets >= 1); 0-4 foreign filters, each a comparison of a joined
+ * column with a constant; joined dimensions of 1-, 2- or 4-byte types, bare or combined with a constant by a binary functor,
+ * into 4 / 2 / 1 byte slots (no float result into a narrow slot).
+ * Declined ("not fusable", nothing launched): numJoins == 0 (AresFusedFilterSelect is the entry point for that) or > 2, a
+ * run-length or mode-0 key column, a Bool or wide (Int64 / Uint64 / GeoPoint / UUID) joined column, a non-null
+ * TimezoneLookup, a join index out of range, everything AresFusedFilterSelect declines, ARES_SELECT=0.  Capacity, zero rows
+ * and a zero limit are as for AresFusedFilterSelect. */
+typedef struct {
+  InputVector key;       /* main-table column the join key comes from: HashLookup's `input` */
+  CuckooHashIndex index; /* HashLookup's `hashIndex` */
+} AresFusedJoin;
+
+typedef struct {
+  int numFilters;
+  AresFusedExpr filters[4]; /* main-table filters, as AresFusedSelect */
+  int numJoins;
+  AresFusedJoin joins[2];
+  int numForeignFilters;
+  AresFusedExpr foreignFilters[4];
+  int foreignFilterJoin[4]; /* the join each foreign filter reads */
+  int numDims;
+  AresFusedExpr dims[8];
+  int dimJoin[8]; /* the join a dimension reads; -1: a main-table column */
+} AresFusedJoinSelect;
+
+CGoCallResHandle AresFusedFilterJoinSelect(const AresFusedJoinSelect *query, int batchRows, int limit /* < 0: none */,
+                                           DimensionVector outKeys, void *cudaStream, int device);
+/* {batches run, batches declined, tiles scanned, rows written, keys probed} of AresFusedFilterJoinSelect since process
+ * start (AresSelectStats counts AresFusedFilterSelect's only) */
+void AresSelectJoinStats(unsigned long long *counters);
 
 #ifdef __cplusplus
 }

@@ -322,6 +322,109 @@ def select_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000,
     return out
 
 
+def select_join_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1), table_keys=(4000, 50_000_000)):
+    """select_leg's query with a join: the trips select plus one 4-byte attribute of a dimension table, selected, once with a
+    foreign filter on it (attr < 500 of 0..999) and once without; limits 100, 1 M and none; through the ordinary sequence
+    (HashLookup over every survivor, filters carrying the record ids, a foreign gather) and through AresFusedFilterJoinSelect on
+    the same build, rows compared as select_leg compares them.  Two table sizes: a few thousand keys joined on city_id (the
+    realistic one, index and attribute cache-resident) and C4's 50 M keys joined on a 4-byte column of random keys `fk`
+    (every probe an HBM access).  One JSON row per (keys, foreign filter, limit, path): ms per step, the per-kernel split, tiles
+    scanned and keys probed."""
+    import cases, harness as H
+    from aresdb_amd import trips
+    from aresdb_amd.executor import Binary, Const
+    from test_scale_parity import build_cuckoo_u32
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(12)
+    batches = trips.trips_shard(rows, batch_rows, seed=11, device=dev)
+    for b in batches:
+        b["key"] = trips.key_column(b["fare"].length, gen, dev)
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    per_batch = 1 << 20
+    out = []
+    for nkeys in table_keys:
+        rng = np.random.default_rng(6)
+        seeds = [int(x) for x in rng.integers(0, 1 << 32, 4)]
+        if nkeys <= 65536:  # joined on city_id (Uint16): keys 0 .. nkeys - 1, the cities among them
+            join_column, key_bytes, num_buckets = "city_id", 2, max(nkeys // 5, 1)
+            table, placed = cases.build_cuckoo([int(k).to_bytes(2, "little") for k in range(nkeys)], 2, num_buckets, seeds, rng,
+                                               record_of=lambda i: (1 + i // per_batch, i % per_batch))
+            attr = rng.integers(0, 1000, nkeys).astype(np.uint32)
+        else:               # joined on `fk`: random keys of the table, 1 % unknown to it
+            join_column, key_bytes, num_buckets = "fk", 4, nkeys // 5
+            keys = rng.permutation(np.arange(1, 4 * nkeys + 1, 4, dtype=np.uint32))[:nkeys]
+            attr = (keys * np.uint32(2654435761) >> np.uint32(20)).astype(np.uint32) % np.uint32(1000)
+            table, _ = build_cuckoo_u32(keys, num_buckets, seeds, per_batch)
+            keys_d = torch.from_numpy(keys.astype(np.int64)).to(dev)
+            for b in batches:
+                n = b["fare"].length
+                pick = keys_d[torch.randint(0, nkeys, (n,), device=dev, generator=gen)]
+                pick = torch.where(torch.rand((n,), device=dev, generator=gen) < 0.01, pick + 1, pick)  # (keys are 1 mod 4)
+                b["fk"] = workload._pack_column(pick.to(torch.int32), None, abi.Uint32)
+            del keys_d
+        names = list(batches[0].keys())
+        vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+        tb = H.Buf(be, table)
+        idx = abi.CuckooHashIndex(); idx.buckets = tb.ptr
+        for i, sd in enumerate(seeds): idx.seeds[i] = sd
+        idx.keyBytes, idx.numHashes, idx.numBuckets = key_bytes, 4, num_buckets
+        nb = (nkeys + per_batch - 1) // per_batch
+        dcols = [H.Column(be, abi.Uint32, attr[b * per_batch:(b + 1) * per_batch]) for b in range(nb)]
+        ft = ForeignTable(join_column=join_column, index=idx, batches={"attr": [c.vp for c in dcols]}, data_types={"attr": abi.Uint32},
+                          base_batch_id=1, num_records_in_last_batch=nkeys - (nb - 1) * per_batch)
+        first = {}
+        for with_filter in (True, False):
+            for limit in limits:
+                for fused in (False, True):
+                    plan = trips.trips_select_plan(limit=limit, fused=fused)
+                    plan.dimensions.insert(2, DimensionSpec(Col("attr", table=1), abi.Uint32))
+                    plan.foreign_tables = [ft]
+                    plan.foreign_filters = [Binary(abi.LessThan, Col("attr", table=1), Const(500))] if with_filter else []
+                    packed = None
+                    def run():
+                        nonlocal packed
+                        q = NativeQuery(be, plan, names, streams=streams)
+                        q.set_max_batch_size(batch_rows)
+                        if packed is None:
+                            packed = q.pack_batches(vps)
+                        q.run_batches(packed)
+                        return q
+                    run().release()
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    for _ in range(steps):
+                        q = run(); q.release()
+                    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+                    be.profiler_enable(True)
+                    stats0 = be.select_join_stats()
+                    q = run(); torch.cuda.synchronize()
+                    kernels = be.profiler_report(); be.profiler_enable(False)
+                    stats1 = be.select_join_stats()
+                    n, fused_batches = q.result_size, q.fused_batches
+                    dims, valids, _ = q.fetch()
+                    q.release()
+                    widths = [abi.DATA_TYPE_BYTES[d.data_type] for d in plan.dimensions]
+                    head = [bytes(d[:w * min(n, 1000000)]) for d, w in zip(dims, widths)] + [bytes(v[:min(n, 1000000)]) for v in valids]
+                    del dims, valids
+                    check = "first"
+                    if not fused:
+                        first[(with_filter, limit)] = (n, head)
+                    else:
+                        check = "ok" if first[(with_filter, limit)] == (n, head) else "MISMATCH against the ordinary sequence"
+                    kernel_ms = sum(ms for c, ms in kernels.values())
+                    out.append({"config": "select_join", "table_keys": nkeys, "join_column": join_column, "foreign_filter": with_filter, "limit": limit,
+                                "path": "extension" if fused else "ordinary", "rows": rows, "batches": len(vps), "batch_rows": batch_rows,
+                                "result_rows": n, "fused_batches": fused_batches, "check": check,
+                                "tiles_scanned": stats1["tiles"] - stats0["tiles"], "keys_probed": stats1["probed"] - stats0["probed"],
+                                "ms_per_step": dt * 1e3, "ms_per_1B_rows": dt * 1e3 * 1e9 / rows,
+                                "kernel_ms_per_step": kernel_ms, "kernel_ms_per_1B_rows": kernel_ms * 1e9 / rows,
+                                "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
+                    print(json.dumps(out[-1]), flush=True)
+        tb.free()
+        for c in dcols:
+            c.free()
+    return out
+
+
 def select_archive_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1), city=7):
     """select_leg's query plus city_id == `city` over ARCHIVE-shaped batches: every batch of the trips shard sorted by
     (city_id, status) and those two columns packed run-length (workload._pack_run_length), as an archive batch stores its
@@ -701,6 +804,10 @@ def main():
     if "select" in which:  # SELECT_BATCH_ROWS / SELECT_LIMITS (comma separated, -1 = none): other batch sizes, fewer limits
         res += select_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                           limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
+    if "selectjoin" in which:  # the same switches as "select"; SELECT_JOIN_KEYS: the table sizes, comma separated
+        res += select_join_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
+                               limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")),
+                               table_keys=tuple(int(float(x)) for x in os.environ.get("SELECT_JOIN_KEYS", "4000,5e7").split(",")))
     if "selectarchive" in which:  # the same switches as "select"
         res += select_archive_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                                   limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
