@@ -597,8 +597,9 @@ class ExplicitGroupBy:
     """GroupByCase's sibling for rows that are GIVEN, not drawn: one or more batches of (dimension rows, validity rows,
     measure values) through HashReduce the way the Go host issues it — every batch is written behind the previous result
     in the input vectors, reduced into the other pair of vectors, and the pairs are swapped.
-    rows / valids: per batch a sequence of tuples, one entry per dimension in vector order; values: per batch a numpy array
-    of `value_dtype`."""
+    rows / valids: per batch a sequence of tuples, one entry per dimension in vector order — or, for slots of any width, a
+    uint8 matrix [rows, width] per dimension and a validity byte column per dimension; values: per batch a numpy array of
+    `value_dtype`."""
 
     def __init__(self, ndw, batches, agg, value_dtype, capacity_slack=3):
         self.ndw = tuple(ndw)
@@ -607,13 +608,18 @@ class ExplicitGroupBy:
         self.vb = self.value_dtype.itemsize
         self.batches = []
         for rows, valids, values in batches:
-            n = len(rows)
-            assert len(valids) == n and len(values) == n
-            rows = np.asarray(rows, dtype=np.uint64).reshape(n, len(self.widths))
-            valids = np.asarray(valids, dtype=np.uint8).reshape(n, len(self.widths))
-            cols = [np.ascontiguousarray(rows[:, d].astype(_SLOT_NP[w])).view(np.uint8) for d, w in enumerate(self.widths)]
-            self.batches.append((cols, [np.ascontiguousarray(valids[:, d]) for d in range(len(self.widths))],
-                                 np.ascontiguousarray(np.asarray(values).astype(self.value_dtype)).view(np.uint8), n))
+            n = len(values)
+            if len(rows) and isinstance(rows[0], np.ndarray) and rows[0].dtype == np.uint8 and rows[0].ndim == 2:  # byte matrices
+                assert [c.shape for c in rows] == [(n, w) for w in self.widths] and [len(o) for o in valids] == [n] * len(self.widths)
+                cols = [np.ascontiguousarray(c).reshape(-1) for c in rows]
+                oks = [np.ascontiguousarray(o, dtype=np.uint8) for o in valids]
+            else:
+                assert len(rows) == n and len(valids) == n
+                rows = np.asarray(rows, dtype=np.uint64).reshape(n, len(self.widths))
+                valids = np.asarray(valids, dtype=np.uint8).reshape(n, len(self.widths))
+                cols = [np.ascontiguousarray(rows[:, d].astype(_SLOT_NP[w])).view(np.uint8) for d, w in enumerate(self.widths)]
+                oks = [np.ascontiguousarray(valids[:, d]) for d in range(len(self.widths))]
+            self.batches.append((cols, oks, np.ascontiguousarray(np.asarray(values).astype(self.value_dtype)).view(np.uint8), n))
         self.capacity = sum(b[3] for b in self.batches) + capacity_slack
 
     def run_hash_reduce(self, be):
@@ -634,6 +640,58 @@ class ExplicitGroupBy:
             size = g
             v.swap()
         v.free()
+        return out
+
+    def run_sort_reduce(self, be, read=("sorted", "after")):
+        """The same batches through Sort + Reduce the way the Go host issues them (query/aql_batchexecutor.go:236-251):
+        InitIndexVector over previous result + batch, Sort, Reduce; dimension, hash and measure vectors ping-ponged, the two
+        index vectors not.  read: "sorted" — the host READS the hash and index vector between Sort and Reduce; "after" — it
+        reads the input's hash / index vector and the output's index vector after Reduce.  One dict per batch: groups, the
+        output rows IN ORDER as a byte matrix [values in slot order][validity bytes], the values, and what was read."""
+        cap = self.capacity
+        dv = [H.DimVector(be, cap, self.ndw, True, False) for _ in range(2)]
+        iv = [H.Buf(be, nbytes=4 * cap) for _ in range(2)]
+        vv = [H.Buf(be, nbytes=self.vb * cap) for _ in range(2)]
+        offs = dv[0].dim_offsets()
+
+        def vec(i):
+            s = dv[i].struct()
+            s.IndexVector = iv[i].ptr
+            return s
+
+        def rows_of(d, n):
+            blob = d.values.read(np.uint8)
+            parts = [blob[vo:vo + n * w].reshape(n, w) for vo, _, w in offs] + [blob[no:no + n].reshape(n, 1) for _, no, _ in offs]
+            return np.concatenate(parts, axis=1)
+
+        out, size = [], 0
+        for cols, oks, values, n in self.batches:
+            for d, (vo, no, w) in enumerate(offs):
+                if n:
+                    dv[0].values.write(cols[d], offset=vo + size * w)
+                    dv[0].values.write(oks[d], offset=no + size)
+            if n:
+                vv[0].write(values, offset=self.vb * size)
+            length = size + n
+            entry = {}
+            be.call("InitIndexVector", iv[0].ptr, 0, length, None, 0)
+            be.call("Sort", vec(0), length, None, 0)
+            if "sorted" in read:
+                entry["hash"] = dv[0].hash.read(np.uint64, length)
+                entry["index"] = iv[0].read(np.uint32, length)
+            g = be.call("Reduce", vec(0), vv[0].ptr, vec(1), vv[1].ptr, self.vb, length, self.agg, None, 0)
+            be.wait()
+            if "after" in read:
+                entry["hash_after"] = dv[0].hash.read(np.uint64, length)
+                entry["index_after"] = iv[0].read(np.uint32, length)
+                entry["out_index"] = iv[1].read(np.uint32, g)
+            entry.update(groups=g, rows=rows_of(dv[1], g), values=vv[1].read(self.value_dtype, g))
+            out.append(entry)
+            size = g
+            dv.reverse()
+            vv.reverse()
+        for x in dv + iv + vv:
+            x.free()
         return out
 
 
