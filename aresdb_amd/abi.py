@@ -163,6 +163,17 @@ class FusedJoinSelect(C.Structure):
                 ("numDims", C.c_int), ("dims", FusedExpr * 8), ("dimJoin", C.c_int * 8)]
 
 
+class JoinedColumn(C.Structure):
+    """AresJoinedColumn (include/ares_extensions.h): one joined column of AresJoinColumnsRun and where it goes"""
+    _fields_ = [("column", InputVector), ("out", C.c_void_p)]
+
+
+class JoinColumns(C.Structure):
+    """AresJoinColumns (include/ares_extensions.h): the query of AresJoinColumnsRun"""
+    _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("join", FusedJoin), ("numColumns", C.c_int),
+                ("columns", JoinedColumn * 4)]
+
+
 # sizes pinned by include/ares_algorithm.h's static assertions (SURVEY.md 8b)
 ABI_SIZES = {CGoCallResHandle: 16, RecordID: 8, CuckooHashIndex: 40, DefaultValue: 24,
              VectorPartySlice: 56, ScratchSpaceVector: 16, ConstantVector: 24,
@@ -334,6 +345,35 @@ class Backend:
         self._algo.AresSelectJoinStats.argtypes, self._algo.AresSelectJoinStats.restype = [C.POINTER(C.c_ulonglong)], None
         self._algo.AresSelectJoinStats(c)
         return {"batches": int(c[0]), "declined": int(c[1]), "tiles": int(c[2]), "rows": int(c[3]), "probed": int(c[4])}
+
+    @property
+    def has_join_columns(self):
+        return hasattr(self._algo, "AresJoinColumnsRun")
+
+    def join_column_bytes(self, rows, dtype):
+        """AresJoinColumnBytes: bytes of one output of AresJoinColumnsRun (bitmap + values, each padded to 64)."""
+        fn = self._algo.AresJoinColumnBytes
+        fn.argtypes, fn.restype = [C.c_int, C.c_int], C.c_size_t
+        return int(fn(int(rows), int(dtype)))
+
+    def join_columns_run(self, query, batch_rows, stream=None, device=0):
+        """AresJoinColumnsRun: the slices of the joined columns, (VectorPartySlice x numColumns); the call does not wait for
+        the stream (AresError, "not fusable: ..." among them, as every call)."""
+        fn = self._algo.AresJoinColumnsRun  # AttributeError: this library has no such entry point
+        fn.argtypes = [C.POINTER(JoinColumns), C.c_int, C.POINTER(VectorPartySlice), _S, _I]
+        fn.restype = CGoCallResHandle
+        slices = (VectorPartySlice * 4)()
+        res = _check(fn(C.byref(query), int(batch_rows), slices, stream, device))
+        assert res == batch_rows
+        return slices
+
+    def join_column_stats(self):
+        """{batches, declined, rows, probed} of AresJoinColumnsRun since the process started; the caller has waited for its
+        streams."""
+        c = (C.c_ulonglong * 4)()
+        self._algo.AresJoinColumnStats.argtypes, self._algo.AresJoinColumnStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresJoinColumnStats(c)
+        return {"batches": int(c[0]), "declined": int(c[1]), "rows": int(c[2]), "probed": int(c[3])}
 
     def select_run_stats(self):
         """{rejected, staged}: tiles of AresFusedFilterSelect thrown away by one run of a run-length filter column, and tiles

@@ -669,10 +669,6 @@ __global__ __launch_bounds__(kSelectBlock, JOINS == 0 ? (RUNS ? 2 : 3) : (RUNS &
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-struct NotFusable : std::runtime_error {
-  explicit NotFusable(const std::string &why) : std::runtime_error("not fusable: " + why) {}
-};
-
 std::atomic<unsigned long long> g_stats[4];     // batches run, batches declined, tiles scanned, rows written
 std::atomic<unsigned long long> g_runStats[2];  // tiles rejected by a run, tiles that staged run ends
 std::atomic<unsigned long long> g_joinStats[5];  // AresFusedFilterJoinSelect: batches run, declined, tiles scanned, rows written, keys probed
@@ -711,11 +707,6 @@ int select_grid(int device, bool runs, int joins) {
   }
   return known[{device, kernel}] = std::max(1, std::min(perCU * cus, kSelectGridCap));
 }
-
-bool wide_type(int t) { return t == Int64 || t == Uint64 || t == GeoPoint || t == UUID; }
-
-// the run-length layout [counts][validity][values] (binding.hpp: mode 3)
-bool run_length_layout(const VectorPartySlice &vp) { return vp.BasePtr && vp.ValuesOffset != 0 && vp.NullsOffset != 0; }
 
 void check_column(const AresFusedExpr &e, int batchRows) {
   if (e.arity != 1 && e.arity != 2) throw NotFusable("arity");
@@ -819,26 +810,6 @@ FastOperands wide_operands(const AresFusedExpr &e, int batchRows, hipStream_t st
   f.functor = Noop;
   f.step = op.step;
   return f;
-}
-
-// a join's key column and index: the conditions and messages of HashLookup
-SelectJoinD bind_join(const AresFusedJoin &j, int batchRows, hipStream_t stream, CallTemps &temps) {
-  if (j.key.Type != VectorPartyInput) throw NotFusable("the join key must be a main-table column");
-  const VectorPartySlice &vp = j.key.Vector.VP;
-  if (!vp.BasePtr) throw NotFusable("mode 0 join key");
-  if (run_length_layout(vp)) throw NotFusable("run-length join key");
-  if (static_cast<int64_t>(vp.Length) < batchRows) throw NotFusable("column shorter than the batch");
-  SelectJoinD J;
-  memset(&J, 0, sizeof(J));
-  try {
-    bind_operand(j.key, true, stream, J.key, temps);
-  } catch (const std::invalid_argument &bad) {
-    throw NotFusable(bad.what());
-  }
-  if (J.key.kind == K_GEO) throw NotFusable("Unsupported data type for HashLookup");
-  if (!cuckoo_geometry_ok(j.index) || !j.index.buckets) throw NotFusable("Unsupported cuckoo hash index geometry");
-  J.index = make_cuckoo(j.index);
-  return J;
 }
 
 // The select scan of one batch; `jq` (may be null): the joins, foreign filters and the joined dimensions of

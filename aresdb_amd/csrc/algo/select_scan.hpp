@@ -5,7 +5,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <stdexcept>
+#include <string>
 
+#include "ares_extensions.h"
+#include "binding.hpp"
 #include "cuckoo_probe.hpp"
 #include "device_model.hpp"
 #include "fast_eval.hpp"
@@ -85,5 +89,35 @@ struct SelectJoinPlanD {
 };
 
 static_assert(sizeof(SelectPlanD) + sizeof(SelectJoinPlanD) <= 4096, "the two plans are the kernel's arguments");
+
+// ---- host side, shared with the joined columns in row space (join_columns.hip) --------------------------------------------
+struct NotFusable : std::runtime_error {
+  explicit NotFusable(const std::string &why) : std::runtime_error("not fusable: " + why) {}
+};
+
+inline bool wide_type(int t) { return t == Int64 || t == Uint64 || t == GeoPoint || t == UUID; }
+
+// the run-length layout [counts][validity][values] (binding.hpp: mode 3)
+inline bool run_length_layout(const VectorPartySlice &vp) { return vp.BasePtr && vp.ValuesOffset != 0 && vp.NullsOffset != 0; }
+
+// a join's key column and index: the conditions and messages of HashLookup
+inline SelectJoinD bind_join(const AresFusedJoin &j, int batchRows, hipStream_t stream, CallTemps &temps) {
+  if (j.key.Type != VectorPartyInput) throw NotFusable("the join key must be a main-table column");
+  const VectorPartySlice &vp = j.key.Vector.VP;
+  if (!vp.BasePtr) throw NotFusable("mode 0 join key");
+  if (run_length_layout(vp)) throw NotFusable("run-length join key");
+  if (static_cast<int64_t>(vp.Length) < batchRows) throw NotFusable("column shorter than the batch");
+  SelectJoinD J;
+  memset(&J, 0, sizeof(J));
+  try {
+    bind_operand(j.key, true, stream, J.key, temps);
+  } catch (const std::invalid_argument &bad) {
+    throw NotFusable(bad.what());
+  }
+  if (J.key.kind == K_GEO) throw NotFusable("Unsupported data type for HashLookup");
+  if (!cuckoo_geometry_ok(j.index) || !j.index.buckets) throw NotFusable("Unsupported cuckoo hash index geometry");
+  J.index = make_cuckoo(j.index);
+  return J;
+}
 
 }  // namespace ares

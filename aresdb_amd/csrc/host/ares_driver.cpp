@@ -17,6 +17,7 @@
 #include <atomic>
 #include <cstdio>
 #include <map>
+#include <memory>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -60,6 +61,8 @@ struct AbiLibrary {
   decltype(&::AresFusedFilterHashReduce) FusedFilterHashReduce = nullptr;  // optional extension
   decltype(&::AresFusedFilterSelect) FusedFilterSelect = nullptr;          // optional extension
   decltype(&::AresFusedFilterJoinSelect) FusedFilterJoinSelect = nullptr;  // optional extension
+  decltype(&::AresJoinColumnsRun) JoinColumnsRun = nullptr;                // optional extension, with ...
+  decltype(&::AresJoinColumnBytes) JoinColumnBytes = nullptr;              // ... the size of one of its outputs
   decltype(&::Expand) Expand;
   // libmem
   decltype(&::DeviceAllocate) DeviceAllocate;
@@ -111,6 +114,8 @@ struct AbiLibrary {
     FusedFilterHashReduce = reinterpret_cast<decltype(FusedFilterHashReduce)>(dlsym(algoHandle, "AresFusedFilterHashReduce"));
     FusedFilterSelect = reinterpret_cast<decltype(FusedFilterSelect)>(dlsym(algoHandle, "AresFusedFilterSelect"));
     FusedFilterJoinSelect = reinterpret_cast<decltype(FusedFilterJoinSelect)>(dlsym(algoHandle, "AresFusedFilterJoinSelect"));
+    JoinColumnsRun = reinterpret_cast<decltype(JoinColumnsRun)>(dlsym(algoHandle, "AresJoinColumnsRun"));
+    JoinColumnBytes = reinterpret_cast<decltype(JoinColumnBytes)>(dlsym(algoHandle, "AresJoinColumnBytes"));
     bind(memHandle, "DeviceAllocate", DeviceAllocate);
     bind(memHandle, "DeviceFree", DeviceFree);
     bind(memHandle, "WaitForCudaStream", WaitForCudaStream);
@@ -254,6 +259,20 @@ struct AresQuery {
   std::vector<RecordID *> foreignRids;
   long calls = 0, fusedBatches = 0;
   bool fusedDeclined = false;  // the library rejected the plan once: stop asking
+  // Joined columns resolved once per batch (AresQuerySetJoinColumns; AresJoinColumnsRun, include/ares_extensions.h): an
+  // aggregation query whose foreign references are all leaf columns of 1-, 2- or 4-byte non-Bool types runs its batches
+  // without base counts over `joinedPlan` — the plan with every such leaf turned into a main-table column behind the batch's
+  // own, the foreign filters appended to the main filters and no foreign tables.
+  struct JoinedTable {
+    std::vector<int> columns;  // the table's columns the query reads, in order of first reference (at most four)
+    int first = 0;             // position of columns[0] among all joined columns
+  };
+  std::vector<JoinedTable> joinedTables;       // one per foreign table
+  std::vector<std::pair<int, int>> joinedLeaves;  // (node of joinedPlan, position among the joined columns)
+  std::unique_ptr<Plan> joinedPlan;            // null: the setter is off or the query is not eligible
+  bool joinColumnsDeclined = false;            // the library rejected the shape once: stop asking
+  std::vector<VectorPartySlice> extendedColumns;  // the batch's columns + the joined ones
+  std::vector<void *> joinedOutputs;              // the joined columns' allocations: released with the batch's input columns
   // non-aggregation queries (query/aql_nonaggr_batchexecutor.go): rows flushed to the host batch by batch
   int maxBatchSize = 0;   // qc.maxBatchSizeAfterPrefilter (AresQuerySetMaxBatchSize); 0: the first batch's size
   int batchRows = 0;      // rows of the current batch BEFORE its filters (batch.Size): what the dimension buffers are sized by
@@ -370,10 +389,16 @@ struct AresQuery {
     stack.pop_back();
   }
 
-  void cleanupBeforeAggregation() {
-    // the batch's input columns go first (query/aql_processor.go:695-699)
+  // the batch's input columns (query/aql_processor.go:695-699), and the joined columns resolved for it
+  void releaseInputColumns() {
     for (void *p : ownedColumns) release(p);
     ownedColumns.clear();
+    for (void *p : joinedOutputs) release(p);
+    joinedOutputs.clear();
+  }
+  void cleanupBeforeAggregation() {
+    // the batch's input columns go first (query/aql_processor.go:695-699)
+    releaseInputColumns();
     release(indexVec); indexVec = nullptr;
     release(predVec); predVec = nullptr;
     for (RecordID *p : foreignRids) release(p);
@@ -844,8 +869,7 @@ struct AresQuery {
     }
     resultSize = static_cast<int>(check(h));
     wait();
-    for (void *p : ownedColumns) release(p);  // the batch's input columns (query/aql_processor.go:695-699)
-    ownedColumns.clear();
+    releaseInputColumns();
     swapResultBuffers();
     fusedBatches++;
     return true;
@@ -910,8 +934,7 @@ struct AresQuery {
     }
     resultSize = static_cast<int>(check(h));
     wait();
-    for (void *p : ownedColumns) release(p);  // the batch's input columns (query/aql_processor.go:695-699)
-    ownedColumns.clear();
+    releaseInputColumns();
     postExecNonAggr();
     fusedBatches++;
     return true;
@@ -941,6 +964,20 @@ struct AresQuery {
       return;
     }
     baseCounts = bc;
+    // a batch whose joined columns were resolved runs as a join-free batch over the rewritten plan and the extended columns
+    struct PlanSwap {
+      Plan &a, *b;
+      PlanSwap(Plan &a_, Plan *b_) : a(a_), b(b_) {
+        if (b) std::swap(a, *b);
+      }
+      ~PlanSwap() {
+        if (b) std::swap(a, *b);
+      }
+    } joined(plan, resolveJoinedColumns(cols, ncols, n) ? joinedPlan.get() : nullptr);
+    if (joined.b) {
+      cols = extendedColumns.data();
+      ncols = static_cast<int>(extendedColumns.size());
+    }
     if (runBatchFused(cols, ncols, n)) {
       swapStreams();
       return;
@@ -953,6 +990,115 @@ struct AresQuery {
     reduce();
     postExec();
     swapStreams();
+  }
+
+  // ---- joined columns in row space (AresJoinColumnsRun, include/ares_extensions.h) ----------------
+  // Decided once per query: builds joinedPlan, or leaves it null.
+  void planJoinedColumns() {
+    joinedPlan.reset();
+    joinedTables.clear();
+    joinedLeaves.clear();
+    if (plan.isNonAggregation || plan.foreign.empty() || !lib->JoinColumnsRun || !lib->JoinColumnBytes) return;
+    if (plan.hasGeo && plan.geo.pointTable != 0) return;  // a geo point from a foreign table
+    const int numNodes = static_cast<int>(plan.nodes.size());
+    std::vector<char> reached(plan.nodes.size(), 0);
+    bool ok = true;
+    // marks what `root` reaches; a foreign leaf below a main-table filter makes the query ineligible
+    auto walk = [&](int root, bool foreignAllowed, auto &&self) -> void {
+      if (root < 0 || root >= numNodes) {
+        ok = false;
+        return;
+      }
+      const AresPlanNode &n = plan.nodes[root];
+      reached[root] = 1;
+      if (n.kind == ARES_NODE_COLUMN && n.table != 0 && !foreignAllowed) ok = false;
+      if (n.kind == ARES_NODE_UNARY || n.kind == ARES_NODE_BINARY) self(n.lhs, foreignAllowed, self);
+      if (n.kind == ARES_NODE_BINARY) self(n.rhs, foreignAllowed, self);
+    };
+    for (int f : plan.filters) walk(f, false, walk);
+    for (int f : plan.foreignFilters) walk(f, true, walk);
+    for (size_t i = 0; i < plan.dimNodes.size(); i++)
+      if (!(plan.hasGeo && plan.geo.dimIndex == static_cast<int>(i))) walk(plan.dimNodes[i], true, walk);
+    walk(plan.measureNode, true, walk);
+    if (!ok) return;
+    joinedTables.assign(plan.foreign.size(), JoinedTable());
+    std::vector<std::pair<int, size_t>> leaves;  // (node, position inside its table's list)
+    for (int i = 0; i < numNodes; i++) {
+      const AresPlanNode &n = plan.nodes[i];
+      if (!reached[i] || n.kind != ARES_NODE_COLUMN || n.table == 0) continue;
+      if (n.table < 0 || n.table > static_cast<int>(plan.foreign.size())) return;
+      const Plan::Foreign &ft = plan.foreign[n.table - 1];
+      if (n.column < 0 || n.column >= ft.t.numColumns) return;
+      const int t = ft.dataTypes[n.column];
+      if (!(t == Int8 || t == Uint8 || t == Int16 || t == Uint16 || t == Int32 || t == Uint32 || t == Float32)) return;
+      std::vector<int> &list = joinedTables[n.table - 1].columns;
+      size_t at = std::find(list.begin(), list.end(), n.column) - list.begin();
+      if (at == list.size()) list.push_back(n.column);
+      if (list.size() > 4) return;
+      leaves.emplace_back(i, at);
+    }
+    int total = 0;
+    for (JoinedTable &jt : joinedTables) {
+      jt.first = total;
+      total += static_cast<int>(jt.columns.size());
+    }
+    joinedPlan.reset(new Plan(plan));
+    for (const auto &leaf : leaves) {
+      AresPlanNode &n = joinedPlan->nodes[leaf.first];
+      joinedLeaves.emplace_back(leaf.first, joinedTables[n.table - 1].first + static_cast<int>(leaf.second));
+      n.table = 0;  // (its column is the batch's column count + the position: set per batch)
+    }
+    joinedPlan->filters.insert(joinedPlan->filters.end(), plan.foreignFilters.begin(), plan.foreignFilters.end());
+    joinedPlan->foreignFilters.clear();
+    joinedPlan->foreign.clear();
+  }
+
+  // One AresJoinColumnsRun per foreign table the query reads, into fresh allocations; extendedColumns = the batch's columns +
+  // the joined ones.  false: this batch takes the original plan (base counts, a decline — then the query stops asking).
+  bool resolveJoinedColumns(const VectorPartySlice *cols, int ncols, int n) {
+    if (!joinedPlan || joinColumnsDeclined || baseCounts || n <= 0) return false;
+    columns = cols;
+    numColumns = ncols;
+    int total = 0;
+    for (const JoinedTable &jt : joinedTables) total += static_cast<int>(jt.columns.size());
+    extendedColumns.assign(cols, cols + ncols);
+    extendedColumns.resize(static_cast<size_t>(ncols + total));
+    for (size_t k = 0; k < joinedTables.size(); k++) {
+      const JoinedTable &jt = joinedTables[k];
+      if (jt.columns.empty()) continue;
+      Pod<AresJoinColumns> q;
+      for (int f : plan.filters)  // pruning hints: the main-table filters of the leaf-versus-constant shape
+        if (q->numFilters < 4 && fusedExpr(f, Bool, &q->filters[q->numFilters]) && q->filters[q->numFilters].arity == 2) q->numFilters++;
+      AresPlanNode leaf;
+      memset(&leaf, 0, sizeof(leaf));
+      leaf.kind = ARES_NODE_COLUMN;
+      leaf.column = plan.foreign[k].t.joinColumn;
+      memcpy(&q->join.key, &columnInput(leaf).get(), sizeof(InputVector));
+      memcpy(&q->join.index, &plan.foreign[k].t.index, sizeof(CuckooHashIndex));
+      q->numColumns = static_cast<int>(jt.columns.size());
+      leaf.table = static_cast<int>(k) + 1;
+      for (size_t c = 0; c < jt.columns.size(); c++) {
+        leaf.column = jt.columns[c];
+        memcpy(&q->columns[c].column, &columnInput(leaf, false).get(), sizeof(InputVector));
+        const size_t bytes = lib->JoinColumnBytes(n, static_cast<DataType>(plan.foreign[k].dataTypes[leaf.column]));
+        joinedOutputs.push_back(alloc(bytes));
+        q->columns[c].out = static_cast<uint8_t *>(joinedOutputs.back());
+      }
+      calls++;
+      CGoCallResHandle h = lib->JoinColumnsRun(&q.get(), n, &extendedColumns[static_cast<size_t>(ncols + jt.first)], stream, device);
+      if (h.pStrErr && strncmp(h.pStrErr, "not fusable", 11) == 0) {
+        free(const_cast<char *>(h.pStrErr));
+        joinColumnsDeclined = true;  // (as fusedDeclined: the plan's shape does not change, stop asking)
+        for (void *p : joinedOutputs) release(p);
+        joinedOutputs.clear();
+        foreignSliceArrays.clear();
+        return false;
+      }
+      check(h);
+    }
+    foreignSliceArrays.clear();  // (the callee has copied the batch descriptors)
+    for (const auto &leafAt : joinedLeaves) joinedPlan->nodes[leafAt.first].column = ncols + leafAt.second;
+    return true;
   }
 };
 
@@ -1028,6 +1174,10 @@ uint8_t *AresQueryMeasureVector(const AresQuery *q) { return q->measureVec[0]; }
 long AresQueryNumCalls(const AresQuery *q) { return q->calls; }
 long AresQueryNumFusedBatches(const AresQuery *q) { return q->fusedBatches; }
 void AresQuerySetLastBatch(AresQuery *q, int isLast) { q->isLastBatch = isLast != 0; }
+void AresQuerySetJoinColumns(AresQuery *q, int on) {
+  if (on) q->planJoinedColumns();
+  else q->joinedPlan.reset();
+}
 void AresQuerySetSecondStream(AresQuery *q, void *stream) { q->otherStream = stream; }
 void AresQueryAdoptColumns(AresQuery *q, void *const *allocations, int count) {
   q->ownedColumns.assign(allocations, allocations + count);

@@ -122,6 +122,17 @@ int AresQueryFetch(AresQuery *q, uint8_t *dims, uint8_t *measures, char *err, in
  * the result is the dimension columns (AresQueryFetch, measures may be NULL), the registers per
  * dimension (uint16 x resultSize) and the encoded HLL vector (query/hll.go:52-63). */
 void AresQuerySetLastBatch(AresQuery *q, int isLast);
+/* Joined columns resolved once per batch, in row space (off by default; AresJoinColumnsRun, include/ares_extensions.h).  Decided
+ * when it is set: an AGGREGATION query (HashReduce, Sort + Reduce or HyperLogLog) whose foreign references — in foreign
+ * filters, dimensions and the measure — are all leaf columns of 1-, 2- or 4-byte non-Bool types, at most four distinct columns
+ * per foreign table and no geo point from a foreign table, gets a rewritten plan: every such leaf is the main-table column
+ * numColumns + j, the foreign filters follow the main filters, and there are no foreign tables.  A batch without base counts
+ * then issues one AresJoinColumnsRun per foreign table the query reads (outputs from DeviceAllocate, the main-table filters of
+ * the column-versus-constant shape as pruning hints) and runs the ordinary steps — the fused extension included — over the
+ * rewritten plan and its columns + the joined ones, which are released with the batch's input columns.  A batch with base
+ * counts takes the original plan; so does a batch the library declines ("not fusable"), after which the query stops asking.
+ * Anything else — a non-aggregation query, a library without the entry point — is untouched. */
+void AresQuerySetJoinColumns(AresQuery *q, int on);
 /* The Go host owns two streams per query and swaps them after every batch
  * (query/aql_processor.go:66-67, :218, :247).  With a second stream set the driver does the same:
  * batch k's calls go to one stream, batch k+1's to the other; fetches use the current one. */

@@ -85,6 +85,7 @@ def _driver():
         lib.AresQueryDestroy.argtypes = [C.c_void_p]
         lib.AresQuerySetLastBatch.argtypes = [C.c_void_p, C.c_int]
         lib.AresQuerySetSecondStream.argtypes = [C.c_void_p, C.c_void_p]
+        lib.AresQuerySetJoinColumns.argtypes, lib.AresQuerySetJoinColumns.restype = [C.c_void_p, C.c_int], None
         lib.AresQuerySetMaxBatchSize.argtypes, lib.AresQuerySetMaxBatchSize.restype = [C.c_void_p, C.c_int], None
         lib.AresQueryAdoptColumns.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]
         lib.AresCommCreate.argtypes, lib.AresCommCreate.restype = [C.c_int, C.c_int, ALLGATHER_FN, C.c_void_p], C.c_void_p
@@ -266,6 +267,11 @@ class NativeQuery:
     def done(self):
         """a non-aggregation query: nothing more is wanted — further batches issue no ABI call"""
         return bool(_driver().AresQueryDone(self._q))
+
+    def set_join_columns(self, on=True):
+        """an aggregation query over joined tables: resolve the joined columns once per batch, in row space, and run the
+        batch as a join-free one (AresQuerySetJoinColumns; off by default, silently without effect where it does not apply)"""
+        _driver().AresQuerySetJoinColumns(self._q, int(bool(on)))
 
     def set_max_batch_size(self, rows):
         """a non-aggregation query: the largest batch it will see (its dimension buffers are allocated once for it)"""

@@ -46,12 +46,15 @@ def run_query(be, plan, batches):
     return out, calls
 
 
-def run_query_native(be, plan, batches, stream=None, streams=None):
+def run_query_native(be, plan, batches, stream=None, streams=None, join_columns=False):
     """The same query through the C++ host driver (libaresdriver.so) instead of the Python mirror.
-    streams: two handles -> batches alternate between them like the Go host (query/aql_processor.go:218)."""
+    streams: two handles -> batches alternate between them like the Go host (query/aql_processor.go:218).
+    join_columns: AresQuerySetJoinColumns — joined columns resolved once per batch, in row space."""
     from .driver import NativeQuery
     names = list(batches[0][0].keys())
     q = NativeQuery(be, plan, names, stream=stream, streams=streams)
+    if join_columns:
+        q.set_join_columns(True)
     if streams:
         stream = streams[0]
     for cols, valid in batches:
@@ -163,6 +166,29 @@ def archive_batch(cols, valid, key):
     return cols, valid, {key: np.concatenate([starts, [len(v)]]).astype(np.uint32)}
 
 
+def stash_table(be, attr, attr_valid, join_column, num_last):
+    """A dimension table of at most four keys 0, 1, ... without any hashing: a cuckoo index with numHashes = 0 whose entries
+    all lie in the stash (memstore/cuckoo_index.go layout: [RecordID x8][signature x8][key x8] per bucket, the stash behind
+    the numBuckets buckets).  Key i -> record (batch 1, index i) of the one-batch column "attr".  (ForeignTable, what to free)"""
+    from .executor import ForeignTable
+    keys = len(attr)
+    assert keys <= 4  # HASH_STASH_SIZE
+    bucket = 8 * (8 + 1 + 4)
+    table = np.zeros(2 * bucket, np.uint8)
+    stash = table[bucket:]
+    stash[:8 * keys].view(np.uint32)[:] = np.stack([np.ones(keys, np.uint32), np.arange(keys, dtype=np.uint32)], axis=1).reshape(-1)
+    stash[64:64 + keys] = 1
+    stash[72:72 + 4 * keys].view(np.uint32)[:] = np.arange(keys, dtype=np.uint32)
+    index_buf = DeviceColumn(be, abi.Uint8, table)
+    column = DeviceColumn(be, abi.Uint32, attr, valid=attr_valid)
+    idx = abi.CuckooHashIndex()
+    idx.buckets = index_buf.vp.BasePtr
+    idx.keyBytes, idx.numHashes, idx.numBuckets = 4, 0, 1
+    ft = ForeignTable(join_column=join_column, index=idx, batches={"attr": [column.vp]}, data_types={"attr": abi.Uint32},
+                      base_batch_id=1, num_records_in_last_batch=num_last)
+    return ft, [index_buf, column]
+
+
 def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
     rng = np.random.default_rng(seed)
     data = [synth_batch(rng, n, null_fraction=0.01) for _ in range(batches)]
@@ -189,3 +215,25 @@ def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
     fused = run_select_native(hip, select_plan(columns, filters, -1, use_fused_extension=True), arch)
     assert plain[0] > 0 and plain[3] == 0 and fused[3] == batches, (plain[0], plain[3], fused[3])
     assert fused[:3] == plain[:3], "the fused select scan and the ordinary sequence disagree on archive-shaped batches"
+    # one tiny joined aggregation (d2 joined to a four-key table: filter on the joined attribute, group by the hour and the
+    # attribute, SUM(m)) both ways through the C++ driver: the per-node join sequence, and the joined column resolved once per
+    # batch in row space (AresJoinColumnsRun) with the batch run as a join-free one
+    from .executor import DimensionSpec, QueryPlan
+    ft, keep = stash_table(hip, np.array([10, 20, 600, 30]), np.array([1, 1, 1, 0], bool), "d2", 4)
+    for use_hash in (True, False):
+        plan = QueryPlan(filters=filters, foreign_tables=[ft], foreign_filters=[Binary(abi.LessThan, Col("attr", table=1), Const(500))],
+                         dimensions=[DimensionSpec(Binary(abi.Floor, Col("ts"), Const(3600)), abi.Uint32),
+                                     DimensionSpec(Col("attr", table=1), abi.Uint32)],
+                         measure=Col("m"), agg=abi.AGGR_SUM_FLOAT, measure_type=abi.Float64, use_hash_reduction=use_hash)
+        before = hip.join_column_stats()
+        per_node, _ = run_query_native(hip, plan, data)
+        assert hip.join_column_stats() == before
+        resolved, _ = run_query_native(hip, plan, data, join_columns=True)
+        assert hip.join_column_stats()["batches"] - before["batches"] == batches
+        assert len(per_node) > 100, len(per_node)
+        compare_results(resolved, per_node)
+    for d in keep:
+        d.free()
+    # the last queries' shapes may still be compiling on the background thread: a process must not run into its exit handlers
+    # with a compilation in flight (the compiler's own statics are torn down under it)
+    hip.rtc_wait()

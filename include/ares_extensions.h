@@ -273,6 +273,51 @@ CGoCallResHandle AresFusedFilterJoinSelect(const AresFusedJoinSelect *query, int
  * start (AresSelectStats counts AresFusedFilterSelect's only) */
 void AresSelectJoinStats(unsigned long long *counters);
 
+/* Joined columns resolved once per batch, in row space: for an AGGREGATION query over a fact table joined to dimension tables.
+ * One kernel of HashLookup's geometry (one probe per lane) probes the key column of a batch without base counts and gathers up
+ * to four joined columns, each written as an ordinary main-table column of the batch's length with a validity bitmap.  The host
+ * then runs the batch as a join-free query over its columns plus these: foreign filters are row-space filters, joined
+ * dimensions are queued transforms, and every fast path of a join-free query applies.  It replaces, for one batch and table,
+ *   HashLookup over the survivors and the record-id vectors every later call of the batch carries.
+ * Output of column c: [bitmap: ceil(rows / 8) bytes, padded to a multiple of 64][values: rows x width, padded to 64] at
+ * columns[c].out, AresJoinColumnBytes(batchRows, type) bytes in all, and
+ *   outSlices[c] = {BasePtr = out, NullsOffset = 0, ValuesOffset = the padded bitmap bytes, StartingIndex = 0,
+ *                   Length = batchRows, DataType = the joined column's, DefaultValue = the foreign column's}.
+ * Row r's (value bits, validity) is what the per-node sequence reads for the record of row r's key, the value stored at the
+ * column's width: a null or missing key, a batch outside the table and an index at or past NumRecordsInLastBatch in the last
+ * batch give (0, null); a mode-0 batch gives the default and the default's validity; a batch with ValuesOffset != 0 takes
+ * validity from its bitmap; any other batch is valid.  Bitmap bits at or past batchRows inside the last written 8-byte word are
+ * 0; bytes past that word are not written.
+ * filters are pruning HINTS, the main-table filters of the query: a row that fails an evaluated hint is not probed and gets
+ * (0, null) — the host's own filters kill it anyway.  A hint the kernel cannot evaluate (anything but a comparison of a
+ * mode-1/2 main-table column of a 1-, 2- or 4-byte type with a constant) is ignored: fewer rows are pruned, nothing else.
+ * Accepted: the key as AresFusedFilterJoinSelect's (a bare main-table column in mode 1 or 2 of any type and index geometry
+ * HashLookup takes); 1-4 joined columns of 1-, 2- or 4-byte non-Bool types (a ForeignColumnInput, fields as for UnaryTransform,
+ * RecordIDs ignored).  Declined ("not fusable", nothing launched): a Bool or wide joined column, a non-null TimezoneLookup, a
+ * mode-0 or run-length key, numColumns outside 1..4, a null or misaligned `out`, ARES_JOIN_COLUMNS=0.
+ * res = batchRows.  The call does not wait for the stream; the outputs are reported to libmem.so as written (AresMemNoteWrite).
+ * Environment (both obey AresReloadEnv): ARES_JOIN_COLUMNS=0 declines always; ARES_JOIN_COLUMNS_GRID=n (tests) sets the
+ * number of workgroups. */
+typedef struct {
+  InputVector column; /* ForeignColumnInput */
+  uint8_t *out;       /* device, 64-byte aligned, AresJoinColumnBytes(batchRows, DataType) bytes */
+} AresJoinedColumn;
+
+typedef struct {
+  int numFilters;
+  AresFusedExpr filters[4]; /* optional pruning hints */
+  AresFusedJoin join;       /* key column + cuckoo index */
+  int numColumns;
+  AresJoinedColumn columns[4];
+} AresJoinColumns;
+
+size_t AresJoinColumnBytes(int rows, enum DataType type); /* 0 for a type the entry point declines */
+CGoCallResHandle AresJoinColumnsRun(const AresJoinColumns *q, int batchRows, VectorPartySlice *outSlices, void *cudaStream,
+                                    int device);
+/* {batches run, batches declined, rows, keys probed} since process start; keys probed = rows that passed every evaluated hint
+ * and had a valid key, counted on the device: the caller has waited for its streams */
+void AresJoinColumnStats(unsigned long long *counters);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,10 +91,11 @@ def c4(be, dev, rows, nkeys):
              "ms": dt * 1e3, "rows_per_s": rows / dt, "kernels": {n: round(ms / c, 4) for n, (c, ms) in k.items()}}]
 
 
-def c4_spec(be, dev, rows, nkeys, batch_rows=1 << 26):
+def c4_spec(be, dev, rows, nkeys, batch_rows=1 << 26, join_columns=False):
     """C4 at BASELINE's stated size: `rows` fact rows in batches of `batch_rows`, an `nkeys`-key cuckoo index
     (every probe an HBM access), one group per key, Sort + Reduce with the previous result merged per batch.
-    Every (fk, attr) -> sum is checked against a torch bincount of the same rows."""
+    Every (fk, attr) -> sum is checked against a torch bincount of the same rows.
+    join_columns (C4_JOIN_COLUMNS=1): AresQuerySetJoinColumns — the joined attribute resolved once per batch, in row space."""
     import harness as H
     from test_scale_parity import build_cuckoo_u32
     rng = np.random.default_rng(6)
@@ -127,6 +128,7 @@ def c4_spec(be, dev, rows, nkeys, batch_rows=1 << 26):
     compiles = -1
     for _ in range(3):
         pq = NativeQuery(be, plan, ["fk", "amount"])
+        pq.set_join_columns(join_columns)
         pn = 1 << 21
         pick = torch.randint(0, len(usable), (pn,), device=dev, generator=g)
         pcf = workload._pack_column(keys_d[pick].to(torch.int32), None, abi.Uint32)
@@ -138,6 +140,8 @@ def c4_spec(be, dev, rows, nkeys, batch_rows=1 << 26):
             break
         compiles = state["compiles"]
     q = NativeQuery(be, plan, ["fk", "amount"])
+    q.set_join_columns(join_columns)
+    probed0 = be.join_column_stats()["probed"]
     kernels, busy = {}, 0.0
     model = {}  # algorithmic bytes per kernel over the whole leg (the C4 table)
     def account(name, nbytes):
@@ -184,7 +188,7 @@ def c4_spec(be, dev, rows, nkeys, batch_rows=1 << 26):
     for x in [tb] + dcols: x.free()
     # HashLookup: one 104-byte bucket probe per row and hash function tried, sector-granular: >= 128 B / row
     look = kernels.get("hash_lookup_kernel")
-    out = {"config": "C4-spec", "rows": rows, "batches": nbatches, "batch_rows": batch_rows, "keys": int(len(usable)),
+    out = {"config": "C4-spec", "join_columns": join_columns, "keys_probed_in_row_space": be.join_column_stats()["probed"] - probed0, "rows": rows, "batches": nbatches, "batch_rows": batch_rows, "keys": int(len(usable)),
            "cuckoo_table_MB": len(table) / 1e6, "cuckoo_build_s": build_s, "groups": groups, "key_level_check": "ok" if ok else "MISMATCH",
            "ms": busy * 1e3, "rows_per_s": rows / busy,
            "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}}
@@ -322,6 +326,121 @@ def select_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000,
     return out
 
 
+def _trips_join_table(be, dev, batches, nkeys, gen, per_batch=1 << 20):
+    """A dimension table for the trips shard with one 4-byte attribute `attr` of 0..999: a few thousand keys joined on city_id
+    (index and attribute cache-resident), or — above 65536 keys — C4's table joined on a 4-byte column `fk` of random keys that
+    is added to every batch, 1 % of them unknown to the table (every probe an HBM access).
+    (ForeignTable, join column, index buffer, attribute columns)"""
+    import cases, harness as H
+    from test_scale_parity import build_cuckoo_u32
+    rng = np.random.default_rng(6)
+    seeds = [int(x) for x in rng.integers(0, 1 << 32, 4)]
+    if nkeys <= 65536:  # joined on city_id (Uint16): keys 0 .. nkeys - 1, the cities among them
+        join_column, key_bytes, num_buckets = "city_id", 2, max(nkeys // 5, 1)
+        table, placed = cases.build_cuckoo([int(k).to_bytes(2, "little") for k in range(nkeys)], 2, num_buckets, seeds, rng,
+                                           record_of=lambda i: (1 + i // per_batch, i % per_batch))
+        attr = rng.integers(0, 1000, nkeys).astype(np.uint32)
+    else:               # joined on `fk`: random keys of the table, 1 % unknown to it
+        join_column, key_bytes, num_buckets = "fk", 4, nkeys // 5
+        keys = rng.permutation(np.arange(1, 4 * nkeys + 1, 4, dtype=np.uint32))[:nkeys]
+        attr = (keys * np.uint32(2654435761) >> np.uint32(20)).astype(np.uint32) % np.uint32(1000)
+        table, _ = build_cuckoo_u32(keys, num_buckets, seeds, per_batch)
+        keys_d = torch.from_numpy(keys.astype(np.int64)).to(dev)
+        for b in batches:
+            n = b["fare"].length
+            pick = keys_d[torch.randint(0, nkeys, (n,), device=dev, generator=gen)]
+            pick = torch.where(torch.rand((n,), device=dev, generator=gen) < 0.01, pick + 1, pick)  # (keys are 1 mod 4)
+            b["fk"] = workload._pack_column(pick.to(torch.int32), None, abi.Uint32)
+        del keys_d
+    tb = H.Buf(be, table)
+    idx = abi.CuckooHashIndex(); idx.buckets = tb.ptr
+    for i, sd in enumerate(seeds): idx.seeds[i] = sd
+    idx.keyBytes, idx.numHashes, idx.numBuckets = key_bytes, 4, num_buckets
+    nb = (nkeys + per_batch - 1) // per_batch
+    dcols = [H.Column(be, abi.Uint32, attr[b * per_batch:(b + 1) * per_batch]) for b in range(nb)]
+    ft = ForeignTable(join_column=join_column, index=idx, batches={"attr": [c.vp for c in dcols]}, data_types={"attr": abi.Uint32},
+                      base_batch_id=1, num_records_in_last_batch=nkeys - (nb - 1) * per_batch)
+    return ft, join_column, tb, dcols
+
+
+def join_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, table_keys=(4000, 50_000_000)):
+    """joinagg: the typical joined aggregation — the trips query (two time filters plus status) joined to a dimension table
+    (select_join_leg's two tables), grouped by the hour and the joined attribute, with the foreign filter attr < 500 on or off:
+    SUM(fare) through HashReduce and COUNT(*) through Sort + Reduce, each through the per-node join sequence and with
+    AresQuerySetJoinColumns on the same build, results compared key by key.  One JSON row per (keys, foreign filter, query,
+    path): wall ms per step, the per-kernel split and the keys probed in row space."""
+    from aresdb_amd import trips
+    from aresdb_amd.executor import Binary, Const
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(12)
+    batches = trips.trips_shard(rows, batch_rows, seed=11, device=dev)
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    out = []
+    for nkeys in table_keys:
+        ft, join_column, tb, dcols = _trips_join_table(be, dev, batches, nkeys, gen)
+        names = list(batches[0].keys())
+        vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+        for with_filter in (True, False):
+            for count in (False, True):
+                first = None
+                for on in (False, True):
+                    plan = trips.trips_plan(count=count)
+                    plan.dimensions[1] = DimensionSpec(Col("attr", table=1), abi.Uint32)
+                    plan.foreign_tables = [ft]
+                    plan.foreign_filters = [Binary(abi.LessThan, Col("attr", table=1), Const(500))] if with_filter else []
+                    packed = None
+                    def run():
+                        nonlocal packed
+                        q = NativeQuery(be, plan, names, streams=streams)
+                        q.set_join_columns(on)
+                        if packed is None:
+                            packed = q.pack_batches(vps)
+                        q.run_batches(packed)
+                        return q
+                    compiles = -1
+                    for _ in range(4):  # priming passes: the shape's kernels are compiled in the background
+                        run().release()
+                        state = be.rtc_wait()
+                        if state is None or state["compiles"] == compiles:
+                            break
+                        compiles = state["compiles"]
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    for _ in range(steps):
+                        run().release()
+                    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+                    be.profiler_enable(True)
+                    stats0 = be.join_column_stats()
+                    q = run(); torch.cuda.synchronize()
+                    kernels = be.profiler_report(); be.profiler_enable(False)
+                    stats1 = be.join_column_stats()
+                    n, calls = q.result_size, q.calls
+                    dims, valids, meas = q.fetch()
+                    q.release()
+                    values = meas.view(np.uint32 if count else np.float64)
+                    keyed = np.stack([dims[0].view(np.uint32), dims[1].view(np.uint32), valids[0].astype(np.uint32), valids[1].astype(np.uint32)], axis=1)
+                    result = {tuple(k): v for k, v in zip(keyed.tolist(), values.tolist())}
+                    check = "first"
+                    if not on:
+                        first = result
+                    elif result == first:
+                        check = "ok"
+                    else:  # (HashReduce groups by a 32-bit hash: which of two colliding rows represents their group depends on the path)
+                        differing = len(set(result.items()) ^ set(first.items()))
+                        check = "%d (key, value) pairs differ; totals %s" % (differing, "equal" if sum(result.values()) == sum(first.values()) else "DIFFER")
+                    kernel_ms = sum(ms for c, ms in kernels.values())
+                    out.append({"config": "joinagg", "table_keys": nkeys, "join_column": join_column, "foreign_filter": with_filter,
+                                "query": "COUNT(*) via Sort+Reduce" if count else "SUM(fare) via HashReduce", "join_columns": on, "rows": rows,
+                                "batches": len(vps), "batch_rows": batch_rows, "groups": n, "abi_calls": calls, "check": check,
+                                "keys_probed_in_row_space": stats1["probed"] - stats0["probed"], "ms_per_step": dt * 1e3,
+                                "ms_per_1B_rows": dt * 1e3 * 1e9 / rows, "kernel_ms_per_step": kernel_ms, "kernel_ms_per_1B_rows": kernel_ms * 1e9 / rows,
+                                "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
+                    print(json.dumps(out[-1]), flush=True)
+        tb.free()
+        for c in dcols:
+            c.free()
+    return out
+
+
 def select_join_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1), table_keys=(4000, 50_000_000)):
     """select_leg's query with a join: the trips select plus one 4-byte attribute of a dimension table, selected, once with a
     foreign filter on it (attr < 500 of 0..999) and once without; limits 100, 1 M and none; through the ordinary sequence
@@ -343,35 +462,9 @@ def select_join_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 100
     per_batch = 1 << 20
     out = []
     for nkeys in table_keys:
-        rng = np.random.default_rng(6)
-        seeds = [int(x) for x in rng.integers(0, 1 << 32, 4)]
-        if nkeys <= 65536:  # joined on city_id (Uint16): keys 0 .. nkeys - 1, the cities among them
-            join_column, key_bytes, num_buckets = "city_id", 2, max(nkeys // 5, 1)
-            table, placed = cases.build_cuckoo([int(k).to_bytes(2, "little") for k in range(nkeys)], 2, num_buckets, seeds, rng,
-                                               record_of=lambda i: (1 + i // per_batch, i % per_batch))
-            attr = rng.integers(0, 1000, nkeys).astype(np.uint32)
-        else:               # joined on `fk`: random keys of the table, 1 % unknown to it
-            join_column, key_bytes, num_buckets = "fk", 4, nkeys // 5
-            keys = rng.permutation(np.arange(1, 4 * nkeys + 1, 4, dtype=np.uint32))[:nkeys]
-            attr = (keys * np.uint32(2654435761) >> np.uint32(20)).astype(np.uint32) % np.uint32(1000)
-            table, _ = build_cuckoo_u32(keys, num_buckets, seeds, per_batch)
-            keys_d = torch.from_numpy(keys.astype(np.int64)).to(dev)
-            for b in batches:
-                n = b["fare"].length
-                pick = keys_d[torch.randint(0, nkeys, (n,), device=dev, generator=gen)]
-                pick = torch.where(torch.rand((n,), device=dev, generator=gen) < 0.01, pick + 1, pick)  # (keys are 1 mod 4)
-                b["fk"] = workload._pack_column(pick.to(torch.int32), None, abi.Uint32)
-            del keys_d
+        ft, join_column, tb, dcols = _trips_join_table(be, dev, batches, nkeys, gen)
         names = list(batches[0].keys())
         vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
-        tb = H.Buf(be, table)
-        idx = abi.CuckooHashIndex(); idx.buckets = tb.ptr
-        for i, sd in enumerate(seeds): idx.seeds[i] = sd
-        idx.keyBytes, idx.numHashes, idx.numBuckets = key_bytes, 4, num_buckets
-        nb = (nkeys + per_batch - 1) // per_batch
-        dcols = [H.Column(be, abi.Uint32, attr[b * per_batch:(b + 1) * per_batch]) for b in range(nb)]
-        ft = ForeignTable(join_column=join_column, index=idx, batches={"attr": [c.vp for c in dcols]}, data_types={"attr": abi.Uint32},
-                          base_batch_id=1, num_records_in_last_batch=nkeys - (nb - 1) * per_batch)
         first = {}
         for with_filter in (True, False):
             for limit in limits:
@@ -799,7 +892,8 @@ def main():
     res = []
     if "c2" in which: res += c2(be, dev, 100_000_000)
     if "c4" in which: res += c4(be, dev, 1 << 26, 200_000)
-    if "c4spec" in which: res += c4_spec(be, dev, int(float(os.environ.get("C4_ROWS", "1e9"))), int(float(os.environ.get("C4_KEYS", "5e7"))))
+    if "c4spec" in which: res += c4_spec(be, dev, int(float(os.environ.get("C4_ROWS", "1e9"))), int(float(os.environ.get("C4_KEYS", "5e7"))),
+                                         join_columns=os.environ.get("C4_JOIN_COLUMNS", "0") == "1")
     if "trips" in which: res += trips_leg(be, dev, int(float(os.environ.get("TRIPS_ROWS", "1e9"))))
     if "select" in which:  # SELECT_BATCH_ROWS / SELECT_LIMITS (comma separated, -1 = none): other batch sizes, fewer limits
         res += select_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
@@ -808,6 +902,9 @@ def main():
         res += select_join_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                                limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")),
                                table_keys=tuple(int(float(x)) for x in os.environ.get("SELECT_JOIN_KEYS", "4000,5e7").split(",")))
+    if "joinagg" in which:  # JOINAGG_ROWS / JOINAGG_BATCH_ROWS; JOINAGG_KEYS: the table sizes, comma separated
+        res += join_agg_leg(be, dev, int(float(os.environ.get("JOINAGG_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("JOINAGG_BATCH_ROWS", str(1 << 26)))),
+                            table_keys=tuple(int(float(x)) for x in os.environ.get("JOINAGG_KEYS", "4000,5e7").split(",")))
     if "selectarchive" in which:  # the same switches as "select"
         res += select_archive_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                                   limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
