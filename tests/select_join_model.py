@@ -67,6 +67,27 @@ class Table:
         self.wide = {"uid": [M.Col(abi.UUID, rng.integers(0, 256, (r, 16), dtype=np.uint8), rng.random(r) < 0.75, starting_index=3),
                              M.Col(abi.UUID, rng.integers(0, 256, (r, 16), dtype=np.uint8)), M.Col(abi.UUID, None)]}
 
+    @classmethod
+    def forged(cls, ix, keys, per_batch):
+        """A table over the bytes and geometry of a cuckoo_model.Index as given — forged signatures, duplicates, stale slots:
+        `placed` is what cuckoo_model.probe answers for each of `keys` (their first key_bytes bytes), not what an inserter did.
+        One Uint32 column "rec" in three mode-1 batches of per_batch records, all inside the table, whose value at
+        (batch b, index i) is b << 16 | i: a joined value names its record."""
+        import cuckoo_model
+        t = cls.__new__(cls)
+        t.key_bytes, t.num_buckets, t.num_hashes, t.seeds = ix.key_bytes, ix.num_buckets, ix.num_hashes, list(ix.seeds)
+        t.per_batch = t.num_last = per_batch
+        t.table = np.array(ix.table, np.uint8)
+        t.placed = {}
+        for k in keys:
+            rec = cuckoo_model.probe(ix, k)
+            if rec != (0, 0):
+                t.placed[bytes(k[:ix.key_bytes])] = rec
+        t.COLUMNS = t.TYPES = {"rec": abi.Uint32}
+        t.cols = {"rec": [M.Col(abi.Uint32, ((BASE_BATCH + b) << 16) | np.arange(per_batch)) for b in range(3)]}
+        t.wide = {}
+        return t
+
     def stash_signatures(self):
         base = self.num_buckets * 8 * (9 + self.key_bytes)
         return self.table[base + 64: base + 68]
@@ -122,7 +143,7 @@ class DeviceTable:
     def index_struct(self):
         hi = abi.CuckooHashIndex()
         hi.buckets = self.index.ptr
-        for i, s in enumerate(SEEDS):
+        for i, s in enumerate(getattr(self.t, "seeds", SEEDS)):
             hi.seeds[i] = s
         hi.keyBytes, hi.numHashes, hi.numBuckets = self.t.key_bytes, self.t.num_hashes, self.t.num_buckets
         return hi
