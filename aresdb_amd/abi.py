@@ -174,6 +174,12 @@ class JoinColumns(C.Structure):
                 ("columns", JoinedColumn * 4)]
 
 
+class GeoShapeColumn(C.Structure):
+    """AresGeoShapeColumn (include/ares_extensions.h): the query of AresGeoShapeColumnRun"""
+    _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("shapes", GeoShapeBatch), ("points", InputVector),
+                ("inOrOut", C.c_int), ("out", C.c_void_p)]
+
+
 # sizes pinned by include/ares_algorithm.h's static assertions (SURVEY.md 8b)
 ABI_SIZES = {CGoCallResHandle: 16, RecordID: 8, CuckooHashIndex: 40, DefaultValue: 24,
              VectorPartySlice: 56, ScratchSpaceVector: 16, ConstantVector: 24,
@@ -374,6 +380,35 @@ class Backend:
         self._algo.AresJoinColumnStats.argtypes, self._algo.AresJoinColumnStats.restype = [C.POINTER(C.c_ulonglong)], None
         self._algo.AresJoinColumnStats(c)
         return {"batches": int(c[0]), "declined": int(c[1]), "rows": int(c[2]), "probed": int(c[3])}
+
+    @property
+    def has_geo_column(self):
+        return hasattr(self._algo, "AresGeoShapeColumnRun")
+
+    def geo_shape_column_bytes(self, rows):
+        """AresGeoShapeColumnBytes: bytes of the output of AresGeoShapeColumnRun (bitmap + one byte per row, each padded to 64)."""
+        fn = self._algo.AresGeoShapeColumnBytes
+        fn.argtypes, fn.restype = [C.c_int], C.c_size_t
+        return int(fn(int(rows)))
+
+    def geo_shape_column_run(self, query, batch_rows, stream=None, device=0):
+        """AresGeoShapeColumnRun: the slice of the shape column; the call does not wait for the stream (AresError, "not
+        fusable: ..." among them, as every call)."""
+        fn = self._algo.AresGeoShapeColumnRun  # AttributeError: this library has no such entry point
+        fn.argtypes = [C.POINTER(GeoShapeColumn), C.c_int, C.POINTER(VectorPartySlice), _S, _I]
+        fn.restype = CGoCallResHandle
+        out = VectorPartySlice()
+        res = _check(fn(C.byref(query), int(batch_rows), C.byref(out), stream, device))
+        assert res == batch_rows
+        return out
+
+    def geo_column_stats(self):
+        """{batches, declined, rows, live, chunks} of AresGeoShapeColumnRun since the process started: live = rows whose polygon
+        walk ran, chunks = wavefront-chunks of 64 list entries walked; the caller has waited for its streams."""
+        c = (C.c_ulonglong * 5)()
+        self._algo.AresGeoShapeColumnStats.argtypes, self._algo.AresGeoShapeColumnStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresGeoShapeColumnStats(c)
+        return {"batches": int(c[0]), "declined": int(c[1]), "rows": int(c[2]), "live": int(c[3]), "chunks": int(c[4])}
 
     def select_run_stats(self):
         """{rejected, staged}: tiles of AresFusedFilterSelect thrown away by one run of a run-length filter column, and tiles

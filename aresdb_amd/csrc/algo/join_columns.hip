@@ -20,6 +20,7 @@
 #include "cuckoo_probe.hpp"
 #include "device_model.hpp"
 #include "fast_eval.hpp"
+#include "row_hints.hpp"
 #include "select_scan.hpp"
 
 namespace ares {
@@ -46,17 +47,6 @@ struct JoinColumnsPlanD {
   unsigned long long *probed;  // the device's counter of keys probed
 };
 static_assert(sizeof(JoinColumnsPlanD) <= 2048, "the plan is the kernel's argument");
-
-// row `row` of a hint's column against its constant: what the row-space filters decide for it
-__device__ __forceinline__ uint32_t hint_keeps(const FastOperands &f, uint32_t row) {
-  const DVal x = read_stored32(reinterpret_cast<const uint8_t *>(f.vals), f.akind, f.step, row, 0);
-  const uint32_t ok = f.nulls ? get_bit(f.nulls, row + f.bitOff) : 1u;
-  DVal y;
-  y.bits = f.bbits;
-  y.ok = f.bok;
-  y = cvt32(y, f.bkind, f.I);
-  return compare_fast(f, x.bits, ok, y);
-}
 
 __global__ __launch_bounds__(kJoinBlock) void join_columns_kernel(JoinColumnsPlanD p, int n) {
   __shared__ unsigned int sProbed;
@@ -136,25 +126,6 @@ size_t padded64(size_t bytes) { return (bytes + 63) / 64 * 64; }
 bool joinable_type(int t) { return t == Int8 || t == Uint8 || t == Int16 || t == Uint16 || t == Int32 || t == Uint32 || t == Float32; }
 
 size_t bitmap_bytes(int rows) { return padded64((static_cast<size_t>(rows > 0 ? rows : 0) + 7) / 8); }
-
-// A hint as the kernel evaluates it, or false: anything but a comparison of a mode-1/2 main-table column of a 1-, 2- or 4-byte
-// type with a constant is left to the host's own filters.
-bool bind_hint(const AresFusedExpr &e, int batchRows, hipStream_t stream, FastOperands &f) {
-  if (e.arity != 2 || e.lhs.Type != VectorPartyInput || e.rhs.Type != ConstantInput) return false;
-  const VectorPartySlice &vp = e.lhs.Vector.VP;
-  if (!vp.BasePtr || run_length_layout(vp) || wide_type(vp.DataType) || static_cast<int64_t>(vp.Length) < batchRows) return false;
-  InputVector ins[2] = {e.lhs, e.rhs};
-  EvalParams p;
-  CallTemps temps;  // (a main-table column and a constant upload nothing)
-  try {
-    build_params(ins, 2, stream, nullptr, nullptr, 0, e.functor, p, temps);
-  } catch (const std::invalid_argument &) {
-    return false;
-  }
-  if (!fast_operands(p, f, true)) return false;
-  f.idx = nullptr;
-  return true;
-}
 
 int join_columns(int device, const AresJoinColumns &q, int batchRows, VectorPartySlice *outSlices, hipStream_t stream) {
   if (!join_columns_enabled()) throw NotFusable("switched off (ARES_JOIN_COLUMNS=0)");

@@ -63,6 +63,8 @@ struct AbiLibrary {
   decltype(&::AresFusedFilterJoinSelect) FusedFilterJoinSelect = nullptr;  // optional extension
   decltype(&::AresJoinColumnsRun) JoinColumnsRun = nullptr;                // optional extension, with ...
   decltype(&::AresJoinColumnBytes) JoinColumnBytes = nullptr;              // ... the size of one of its outputs
+  decltype(&::AresGeoShapeColumnRun) GeoShapeColumnRun = nullptr;          // optional extension, with ...
+  decltype(&::AresGeoShapeColumnBytes) GeoShapeColumnBytes = nullptr;      // ... the size of its output
   decltype(&::Expand) Expand;
   // libmem
   decltype(&::DeviceAllocate) DeviceAllocate;
@@ -116,6 +118,8 @@ struct AbiLibrary {
     FusedFilterJoinSelect = reinterpret_cast<decltype(FusedFilterJoinSelect)>(dlsym(algoHandle, "AresFusedFilterJoinSelect"));
     JoinColumnsRun = reinterpret_cast<decltype(JoinColumnsRun)>(dlsym(algoHandle, "AresJoinColumnsRun"));
     JoinColumnBytes = reinterpret_cast<decltype(JoinColumnBytes)>(dlsym(algoHandle, "AresJoinColumnBytes"));
+    GeoShapeColumnRun = reinterpret_cast<decltype(GeoShapeColumnRun)>(dlsym(algoHandle, "AresGeoShapeColumnRun"));
+    GeoShapeColumnBytes = reinterpret_cast<decltype(GeoShapeColumnBytes)>(dlsym(algoHandle, "AresGeoShapeColumnBytes"));
     bind(memHandle, "DeviceAllocate", DeviceAllocate);
     bind(memHandle, "DeviceFree", DeviceFree);
     bind(memHandle, "WaitForCudaStream", WaitForCudaStream);
@@ -273,6 +277,14 @@ struct AresQuery {
   bool joinColumnsDeclined = false;            // the library rejected the shape once: stop asking
   std::vector<VectorPartySlice> extendedColumns;  // the batch's columns + the joined ones
   std::vector<void *> joinedOutputs;              // the joined columns' allocations: released with the batch's input columns
+  // The geofence verdict resolved once per batch (AresQuerySetGeoColumn; AresGeoShapeColumnRun, include/ares_extensions.h): an
+  // aggregation query with a geo intersection over a main-table point column and no foreign tables runs its batches without
+  // base counts over `geoPlan` — the plan without geo, with one more filter `shape column < 128` (true for every valid value,
+  // null for a null one) and the geo dimension, if there is one, as the bare column.  The column's allocation goes to
+  // joinedOutputs; extendedColumns holds the batch's columns + it.
+  std::unique_ptr<Plan> geoPlan;   // null: the setter is off or the query is not eligible
+  int geoLeaf = -1;                // node of geoPlan that is the shape column
+  bool geoColumnDeclined = false;  // the library rejected the shape once: stop asking
   // non-aggregation queries (query/aql_nonaggr_batchexecutor.go): rows flushed to the host batch by batch
   int maxBatchSize = 0;   // qc.maxBatchSizeAfterPrefilter (AresQuerySetMaxBatchSize); 0: the first batch's size
   int batchRows = 0;      // rows of the current batch BEFORE its filters (batch.Size): what the dimension buffers are sized by
@@ -964,7 +976,8 @@ struct AresQuery {
       return;
     }
     baseCounts = bc;
-    // a batch whose joined columns were resolved runs as a join-free batch over the rewritten plan and the extended columns
+    // a batch whose joined columns were resolved runs as a join-free batch over the rewritten plan and the extended columns;
+    // so does, as a geo-free batch, one whose geofence verdicts were (a query is eligible for one of the two at most)
     struct PlanSwap {
       Plan &a, *b;
       PlanSwap(Plan &a_, Plan *b_) : a(a_), b(b_) {
@@ -973,7 +986,7 @@ struct AresQuery {
       ~PlanSwap() {
         if (b) std::swap(a, *b);
       }
-    } joined(plan, resolveJoinedColumns(cols, ncols, n) ? joinedPlan.get() : nullptr);
+    } joined(plan, resolveJoinedColumns(cols, ncols, n) ? joinedPlan.get() : resolveGeoColumn(cols, ncols, n) ? geoPlan.get() : nullptr);
     if (joined.b) {
       cols = extendedColumns.data();
       ncols = static_cast<int>(extendedColumns.size());
@@ -1100,6 +1113,80 @@ struct AresQuery {
     for (const auto &leafAt : joinedLeaves) joinedPlan->nodes[leafAt.first].column = ncols + leafAt.second;
     return true;
   }
+
+  // ---- the geofence verdict in row space (AresGeoShapeColumnRun, include/ares_extensions.h) --------
+  // Decided once per query: builds geoPlan, or leaves it null.
+  void planGeoColumn() {
+    geoPlan.reset();
+    geoLeaf = -1;
+    if (plan.isNonAggregation || !plan.hasGeo || !lib->GeoShapeColumnRun || !lib->GeoShapeColumnBytes) return;
+    if (plan.geo.pointTable != 0 || !plan.geo.shapeLatLongs) return;
+    if (!plan.foreign.empty() || !plan.foreignFilters.empty()) return;
+    const int dim = plan.geo.dimIndex;
+    if (dim >= 0 && !plan.geo.inOrOut) return;  // (every kept row is outside every shape: the reference writes no dimension row)
+    if (dim >= static_cast<int>(plan.dimNodes.size())) return;
+    if (dim >= 0 && data_type_bytes(plan.dimTypes[dim]) != 1) return;  // (the shape number lives in a 1-byte slot)
+    geoPlan.reset(new Plan(plan));
+    Plan &g = *geoPlan;
+    g.hasGeo = false;
+    AresPlanNode leaf, bound, less;
+    memset(&leaf, 0, sizeof(leaf));
+    leaf.kind = ARES_NODE_COLUMN;  // (table 0; its column is the batch's column count: set per batch)
+    memset(&bound, 0, sizeof(bound));
+    bound.kind = ARES_NODE_CONST_INT;
+    bound.ival = 128;
+    geoLeaf = static_cast<int>(g.nodes.size());
+    memset(&less, 0, sizeof(less));
+    less.kind = ARES_NODE_BINARY;
+    less.op = LessThan;
+    less.lhs = geoLeaf;
+    less.rhs = geoLeaf + 1;
+    less.outType = Bool;
+    g.nodes.push_back(leaf);
+    g.nodes.push_back(bound);
+    g.nodes.push_back(less);
+    g.filters.push_back(geoLeaf + 2);
+    if (dim >= 0) {
+      g.dimNodes[dim] = geoLeaf;
+      g.dimTypes[dim] = Uint8;
+    }
+  }
+
+  // One AresGeoShapeColumnRun into a fresh allocation; extendedColumns = the batch's columns + the shape column.  false: this
+  // batch takes the original plan (base counts, a decline — then the query stops asking).
+  bool resolveGeoColumn(const VectorPartySlice *cols, int ncols, int n) {
+    if (!geoPlan || geoColumnDeclined || baseCounts || n <= 0) return false;
+    columns = cols;
+    numColumns = ncols;
+    Pod<AresGeoShapeColumn> q;
+    for (int f : plan.filters)  // pruning hints: the main-table filters of the leaf-versus-constant shape
+      if (q->numFilters < 4 && fusedExpr(f, Bool, &q->filters[q->numFilters]) && q->filters[q->numFilters].arity == 2) q->numFilters++;
+    q->shapes.LatLongs = const_cast<uint8_t *>(plan.geo.shapeLatLongs);
+    q->shapes.TotalNumPoints = plan.geo.totalNumPoints;
+    q->shapes.TotalWords = static_cast<uint8_t>((plan.geo.numShapes + 31) / 32);
+    AresPlanNode pointNode;
+    memset(&pointNode, 0, sizeof(pointNode));
+    pointNode.kind = ARES_NODE_COLUMN;
+    pointNode.column = plan.geo.pointColumn;
+    memcpy(&q->points, &columnInput(pointNode).get(), sizeof(InputVector));
+    q->inOrOut = plan.geo.inOrOut;
+    void *out = alloc(lib->GeoShapeColumnBytes(n));
+    q->out = static_cast<uint8_t *>(out);
+    extendedColumns.assign(cols, cols + ncols);
+    extendedColumns.resize(static_cast<size_t>(ncols) + 1);
+    calls++;
+    CGoCallResHandle h = lib->GeoShapeColumnRun(&q.get(), n, &extendedColumns[static_cast<size_t>(ncols)], stream, device);
+    if (h.pStrErr && strncmp(h.pStrErr, "not fusable", 11) == 0) {
+      free(const_cast<char *>(h.pStrErr));
+      geoColumnDeclined = true;  // (as fusedDeclined: the plan's shape does not change, stop asking)
+      release(out);
+      return false;
+    }
+    joinedOutputs.push_back(out);  // (released with the batch's input columns, also when the call failed)
+    check(h);
+    geoPlan->nodes[static_cast<size_t>(geoLeaf)].column = ncols;
+    return true;
+  }
 };
 
 // ---- C API ---------------------------------------------------------------------------------------
@@ -1177,6 +1264,10 @@ void AresQuerySetLastBatch(AresQuery *q, int isLast) { q->isLastBatch = isLast !
 void AresQuerySetJoinColumns(AresQuery *q, int on) {
   if (on) q->planJoinedColumns();
   else q->joinedPlan.reset();
+}
+void AresQuerySetGeoColumn(AresQuery *q, int on) {
+  if (on) q->planGeoColumn();
+  else q->geoPlan.reset();
 }
 void AresQuerySetSecondStream(AresQuery *q, void *stream) { q->otherStream = stream; }
 void AresQueryAdoptColumns(AresQuery *q, void *const *allocations, int count) {

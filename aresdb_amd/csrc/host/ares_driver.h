@@ -133,6 +133,19 @@ void AresQuerySetLastBatch(AresQuery *q, int isLast);
  * counts takes the original plan; so does a batch the library declines ("not fusable"), after which the query stops asking.
  * Anything else — a non-aggregation query, a library without the entry point — is untouched. */
 void AresQuerySetJoinColumns(AresQuery *q, int on);
+/* The geofence verdict resolved once per batch, in row space (off by default; AresGeoShapeColumnRun, include/ares_extensions.h).
+ * Decided when it is set: an AGGREGATION query (HashReduce, Sort + Reduce or HyperLogLog) with a geo intersection whose points are
+ * a main-table column (geo.pointTable == 0, shapes on the device), without foreign tables or foreign filters, and not one that
+ * asks for the shape dimension of the rows OUTSIDE every shape (dimIndex >= 0 with inOrOut == 0), gets a rewritten plan: no geo
+ * intersection, one more main-table filter `shape column < 128` (true for every valid byte, null — so false — for a null one),
+ * and the geo dimension, if any, as that bare Uint8 column in its 1-byte slot.  A batch without base counts then issues one
+ * AresGeoShapeColumnRun (output from DeviceAllocate, the main-table filters of the column-versus-constant shape as pruning
+ * hints) and runs the ordinary steps — the fused extension included — over the rewritten plan and its columns + the shape column
+ * (main-table column numColumns), which is released with the batch's input columns.  A batch with base counts takes the original
+ * plan; so does a batch the library declines ("not fusable"), after which the query stops asking.  Anything else — a
+ * non-aggregation query, geo points from a joined table, a plan with foreign tables, a library without the entry point — is
+ * untouched. */
+void AresQuerySetGeoColumn(AresQuery *q, int on);
 /* The Go host owns two streams per query and swaps them after every batch
  * (query/aql_processor.go:66-67, :218, :247).  With a second stream set the driver does the same:
  * batch k's calls go to one stream, batch k+1's to the other; fetches use the current one. */

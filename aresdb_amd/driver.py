@@ -86,6 +86,7 @@ def _driver():
         lib.AresQuerySetLastBatch.argtypes = [C.c_void_p, C.c_int]
         lib.AresQuerySetSecondStream.argtypes = [C.c_void_p, C.c_void_p]
         lib.AresQuerySetJoinColumns.argtypes, lib.AresQuerySetJoinColumns.restype = [C.c_void_p, C.c_int], None
+        lib.AresQuerySetGeoColumn.argtypes, lib.AresQuerySetGeoColumn.restype = [C.c_void_p, C.c_int], None
         lib.AresQuerySetMaxBatchSize.argtypes, lib.AresQuerySetMaxBatchSize.restype = [C.c_void_p, C.c_int], None
         lib.AresQueryAdoptColumns.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int]
         lib.AresCommCreate.argtypes, lib.AresCommCreate.restype = [C.c_int, C.c_int, ALLGATHER_FN, C.c_void_p], C.c_void_p
@@ -272,6 +273,12 @@ class NativeQuery:
         """an aggregation query over joined tables: resolve the joined columns once per batch, in row space, and run the
         batch as a join-free one (AresQuerySetJoinColumns; off by default, silently without effect where it does not apply)"""
         _driver().AresQuerySetJoinColumns(self._q, int(bool(on)))
+
+    def set_geo_column(self, on=True):
+        """an aggregation query with a geo intersection over a main-table point column: resolve the geofence verdict once per
+        batch, in row space, and run the batch as a geo-free one (AresQuerySetGeoColumn; off by default, silently without
+        effect where it does not apply)"""
+        _driver().AresQuerySetGeoColumn(self._q, int(bool(on)))
 
     def set_max_batch_size(self, rows):
         """a non-aggregation query: the largest batch it will see (its dimension buffers are allocated once for it)"""

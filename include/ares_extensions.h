@@ -318,6 +318,50 @@ CGoCallResHandle AresJoinColumnsRun(const AresJoinColumns *q, int batchRows, Vec
  * and had a valid key, counted on the device: the caller has waited for its streams */
 void AresJoinColumnStats(unsigned long long *counters);
 
+/* The geofence verdict of a batch resolved once, in row space: for an AGGREGATION query with a geography_intersects join whose
+ * points are a main-table column.  One kernel classifies every row of a batch without base counts (pruning hints, null
+ * points), compacts the live rows of each 1024-row tile in LDS and walks the polygon edges over them alone, as
+ * GeoBatchIntersects' kernel walks them over the index vector; the verdict of row r is ONE byte of an ordinary mode-2 Uint8
+ * main-table column.  The host then runs the batch as a geo-free query over its columns plus this one: the byte's validity is
+ * the geo filter (a comparison of the column with a constant is null, hence false, for a null row), its value the geo
+ * dimension, and every fast path of a geo-free query applies.  It replaces, for one batch,
+ *   GeoBatchIntersects over the survivors, the predicate words it leaves, and WriteGeoShapeDim.
+ * Output: [bitmap: ceil(rows / 8) bytes, padded to a multiple of 64][values: rows bytes, padded to 64] at `out`,
+ * AresGeoShapeColumnBytes(batchRows) bytes in all (== AresJoinColumnBytes(batchRows, Uint8): the same layout), and
+ *   *outSlice = {BasePtr = out, NullsOffset = 0, ValuesOffset = the padded bitmap bytes, StartingIndex = 0,
+ *                Length = batchRows, DataType = Uint8}.
+ * Bitmap bits at or past batchRows inside the last written 8-byte word are 0; bytes past that word are not written.
+ * Row r: let `words` be what GeoBatchIntersects leaves in a predicate vector that started at zero for an entry whose index is
+ * r, and s the first set bit of the words read as an int8 (shapes 128..255 read as none, -1).  Row r is VALID iff
+ * (s < 0) != inOrOut — exactly the rows GeoBatchIntersects keeps —; its value is s when inOrOut != 0 and the row is valid,
+ * 0 otherwise.  A null point follows the first-edge rule: with TotalNumPoints >= 2 and shape[0] == shape[1] it is null
+ * whichever way the filter asks; otherwise its words stay zero, so it is null when inOrOut != 0 and valid with value 0 when
+ * inOrOut == 0.  TotalNumPoints == 0 toggles nothing.
+ * filters are pruning HINTS exactly as AresJoinColumns::filters: a row that fails an evaluated hint is not walked and gets
+ * (0, null); a hint the kernel cannot evaluate is ignored.
+ * Accepted: a GeoPoint main-table column in mode 1 or 2.  Declined ("not fusable", nothing launched, nothing written): a mode-0
+ * or run-length point column, a column shorter than batchRows, a joined (ForeignColumnInput) point column, a null or misaligned
+ * `out`, ARES_GEO_COLUMN=0.  TotalWords outside 1..8 is GeoBatchIntersects' error.
+ * res = batchRows.  The call does not wait for the stream; the output is reported to libmem.so as written (AresMemNoteWrite).
+ * Environment (both obey AresReloadEnv): ARES_GEO_COLUMN=0 declines always; ARES_GEO_COLUMN_GRID=n (tests) sets the number of
+ * workgroups. */
+typedef struct {
+  int numFilters;
+  AresFusedExpr filters[4]; /* optional pruning hints, as AresJoinColumns::filters */
+  GeoShapeBatch shapes;     /* as GeoBatchIntersects takes it */
+  InputVector points;       /* VectorPartyInput, GeoPoint, main table */
+  int inOrOut;
+  uint8_t *out;             /* device, 64-byte aligned, AresGeoShapeColumnBytes(batchRows) bytes */
+} AresGeoShapeColumn;
+
+size_t AresGeoShapeColumnBytes(int rows);
+CGoCallResHandle AresGeoShapeColumnRun(const AresGeoShapeColumn *q, int batchRows, VectorPartySlice *outSlice, void *cudaStream,
+                                       int device);
+/* {batches run, batches declined, rows, live rows, wavefront-chunks walked} since process start; live rows = rows that passed
+ * every evaluated hint and had a valid point, wavefront-chunks = the sum over tiles of ceil(live rows of the tile / 64), both
+ * counted on the device: the caller has waited for its streams */
+void AresGeoShapeColumnStats(unsigned long long *counters);
+
 #ifdef __cplusplus
 }
 #endif

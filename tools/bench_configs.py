@@ -854,10 +854,8 @@ def hll(be, dev, rows, groups, users, batches=2):
              "kernel_total_ms": {n_: round(ms, 3) for n_, (c, ms) in sorted(k.items(), key=lambda kv: -kv[1][1])}}]
 
 
-def geo(be, dev, rows, num_shapes, pts_per_shape):
-    """geography_intersects filter + shape dimension + COUNT over `rows` points."""
-    import harness as H
-    from aresdb_amd.executor import Const, GeoIntersection
+def _geo_shapes(num_shapes, pts_per_shape):
+    """`num_shapes` closed rings of `pts_per_shape` vertices, radii 3..12 degrees, centres uniform over +-80: (lats, longs, shape numbers)"""
     rng = np.random.default_rng(9)
     lats, longs, sidx = [], [], []
     for sh in range(num_shapes):
@@ -865,6 +863,15 @@ def geo(be, dev, rows, num_shapes, pts_per_shape):
         ang = np.sort(rng.uniform(0, 2 * np.pi, pts_per_shape)); rad = rng.uniform(3, 12)
         ys, xs = (cy + rad * np.sin(ang)).astype(np.float32), (cx + rad * np.cos(ang)).astype(np.float32)
         lats += list(ys) + [ys[0]]; longs += list(xs) + [xs[0]]; sidx += [sh] * (pts_per_shape + 1)
+    return lats, longs, sidx
+
+
+def geo(be, dev, rows, num_shapes, pts_per_shape, geo_column=False):
+    """geography_intersects filter + shape dimension + COUNT over `rows` points.  geo_column (GEO_COLUMN=1):
+    AresQuerySetGeoColumn — the verdict resolved in row space; no filter, every row live: the shape where row space gains nothing."""
+    import harness as H
+    from aresdb_amd.executor import Const, GeoIntersection
+    lats, longs, sidx = _geo_shapes(num_shapes, pts_per_shape)
     shapes = H.GeoShapes(be, np.float32(lats), np.float32(longs), sidx, num_shapes)
     plan = QueryPlan(filters=[], dimensions=[DimensionSpec(Const(0), abi.Uint8)], measure=Const(1), agg=abi.AGGR_SUM_UNSIGNED,
                      measure_type=abi.Uint32, use_hash_reduction=False,
@@ -874,15 +881,114 @@ def geo(be, dev, rows, num_shapes, pts_per_shape):
     vp = abi.VectorPartySlice()
     vp.BasePtr, vp.NullsOffset, vp.ValuesOffset, vp.DataType, vp.Length, vp.StartingIndex = pts.data_ptr(), 0, 0, abi.GeoPoint, rows, 0
     def run():
-        q = NativeQuery(be, plan, ["pt"]); q.run({"pt": vp}, rows)
+        q = NativeQuery(be, plan, ["pt"]); q.set_geo_column(geo_column); q.run({"pt": vp}, rows)
         n = q.result_size
         m = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         be.call("AsyncCopyDeviceToDevice", m.data_ptr(), q.measure_vector, 4 * n, None, 0); be.wait()
         tot = int(m[:n].to(torch.int64).sum()); q.release(); return n, tot
     dt, k, (n, inside) = timed(be, run)
-    return [{"config": "GEO", "rows": rows, "shapes": num_shapes, "polygon_points": len(lats), "groups": n, "inside": inside,
+    shapes.free()
+    return [{"config": "GEO", "geo_column": geo_column, "rows": rows, "shapes": num_shapes, "polygon_points": len(lats), "groups": n, "inside": inside,
              "ms": dt * 1e3, "rows_per_s": rows / dt, "edge_tests_per_s": rows * (len(lats) - 1) / dt,
              "kernels": {n_: round(ms / c, 4) for n_, (c, ms) in k.items()}}]
+
+
+def geo_query_leg(be, dev, rows, batch_rows=1 << 26, steps=3, shape_sets=((100, 20), (250, 400))):
+    """geoquery: trips per geofence — the trips table plus a GeoPoint column (5 % null points, uniform over +-100 degrees), two time
+    filters that keep 2 of the 8 days and status == completed, grouped by the hour and the shape: COUNT(*) through Sort + Reduce and
+    SUM(fare) through HashReduce, each through the per-node geo sequence and with AresQuerySetGeoColumn on the same build, results
+    compared key by key.  One JSON row per (shapes, query, path): wall ms per step (median of `steps`), the per-kernel split, and
+    for the row-space kernel the live rows, the wavefront-chunks walked and the edge tests per second over live rows."""
+    import harness as H
+    from aresdb_amd import trips
+    from aresdb_amd.executor import Const, GeoIntersection
+    from aresdb_amd.workload import ResidentColumn, _align64
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(14)
+    batches = trips.trips_shard(rows, batch_rows, seed=13, device=dev)
+    for b in batches:
+        n = b["fare"].length
+        pts = (torch.rand((n, 2), device=dev, generator=gen) * 200 - 100).to(torch.float32).contiguous().view(torch.uint8).reshape(-1)
+        valid = (torch.rand((n,), dtype=torch.float32, device=dev, generator=gen) >= 0.05).to(torch.uint8)
+        nb = (n + 7) // 8
+        if nb * 8 != n:
+            valid = torch.cat([valid, torch.zeros(nb * 8 - n, dtype=torch.uint8, device=dev)])
+        weights = (1 << torch.arange(8, device=dev, dtype=torch.int32)).to(torch.uint8)
+        off = _align64(nb)
+        blob = torch.zeros(off + pts.numel() + 64, dtype=torch.uint8, device=dev)
+        blob[:nb] = (valid.view(nb, 8) * weights).sum(dim=1, dtype=torch.int32).to(torch.uint8)
+        blob[off:off + pts.numel()] = pts
+        b["pt"] = ResidentColumn(blob, off, abi.GeoPoint, n, True)
+        del pts, valid
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    names = list(batches[0].keys())
+    vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+    time_range = (86400 * 3, 86400 * 5)
+    out = []
+    for num_shapes, pts_per_shape in shape_sets:
+        lats, longs, sidx = _geo_shapes(num_shapes, pts_per_shape)
+        shapes = H.GeoShapes(be, np.float32(lats), np.float32(longs), sidx, num_shapes)
+        for count in (True, False):
+            first = None
+            for on in (False, True):
+                plan = trips.trips_plan(count=count, time_range=time_range)
+                plan.dimensions[1] = DimensionSpec(Const(0), abi.Uint8)  # placeholder: the shape number
+                plan.geo = GeoIntersection(shapes.buf.ptr, num_shapes, len(lats), "pt", 0, True, 1)
+                packed = None
+                def run():
+                    nonlocal packed
+                    q = NativeQuery(be, plan, names, streams=streams)
+                    q.set_geo_column(on)
+                    if packed is None:
+                        packed = q.pack_batches(vps)
+                    q.run_batches(packed)
+                    return q
+                compiles = -1
+                for _ in range(4):  # priming passes: the shape's kernels are compiled in the background
+                    run().release()
+                    state = be.rtc_wait()
+                    if state is None or state["compiles"] == compiles:
+                        break
+                    compiles = state["compiles"]
+                times = []
+                for _ in range(steps):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    run().release()
+                    torch.cuda.synchronize(); times.append(time.perf_counter() - t0)
+                dt = float(np.median(times))
+                be.profiler_enable(True)
+                stats0 = be.geo_column_stats()
+                q = run(); torch.cuda.synchronize()
+                kernels = be.profiler_report(); be.profiler_enable(False)
+                stats1 = be.geo_column_stats()
+                n, calls = q.result_size, q.calls
+                dims, valids, meas = q.fetch()
+                q.release()
+                values = meas.view(np.uint32 if count else np.float64)
+                keyed = np.stack([dims[0].view(np.uint32), dims[1].astype(np.uint32), valids[0].astype(np.uint32), valids[1].astype(np.uint32)], axis=1)
+                result = {tuple(k): v for k, v in zip(keyed.tolist(), values.tolist())}
+                check = "first"
+                if not on:
+                    first = result
+                elif result == first:
+                    check = "ok"
+                else:  # (HashReduce groups by a 32-bit hash: which of two colliding rows represents their group depends on the path)
+                    differing = len(set(result.items()) ^ set(first.items()))
+                    check = "%d (key, value) pairs differ; totals %s" % (differing, "equal" if sum(result.values()) == sum(first.values()) else "DIFFER")
+                live, chunks = stats1["live"] - stats0["live"], stats1["chunks"] - stats0["chunks"]
+                walk = {k: ms for k, (c, ms) in kernels.items() if k.startswith("geo_shape_column_kernel") or k.startswith("geo_intersect_kernel")}
+                walk_ms = sum(walk.values())
+                kernel_ms = sum(ms for c, ms in kernels.values())
+                out.append({"config": "geoquery", "shapes": num_shapes, "polygon_points": len(lats),
+                            "query": "COUNT(*) via Sort+Reduce" if count else "SUM(fare) via HashReduce", "geo_column": on, "rows": rows,
+                            "batches": len(vps), "batch_rows": batch_rows, "groups": n, "abi_calls": calls, "check": check,
+                            "live_rows": live, "wavefront_chunks": chunks, "lanes_filled": live / (64.0 * chunks) if chunks else None,
+                            "walk_kernel_ms": walk_ms, "edge_tests_per_s_over_live_rows": live * (len(lats) - 1) / (walk_ms * 1e-3) if on and walk_ms else None,
+                            "step_times_ms": [t * 1e3 for t in times], "ms_per_step": dt * 1e3, "kernel_ms_per_step": kernel_ms,
+                            "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
+                print(json.dumps(out[-1]), flush=True)
+        shapes.free()
+    return out
 
 
 def main():
@@ -915,7 +1021,11 @@ def main():
         if leg in which: res += sort_avg_legs(be, dev, leg, int(float(os.environ.get("SORT_AVG_ROWS", "1e9"))))
     if "hll" in which:
         res += hll(be, dev, 1 << 25, 1000, 5_000_000) + hll(be, dev, 1 << 25, 4, 50_000_000) + hll(be, dev, 1 << 25, 100, 50_000_000, batches=4)
-    if "geo" in which: res += geo(be, dev, 1 << 24, 100, 20) + geo(be, dev, 1 << 22, 250, 400)
+    if "geo" in which:  # GEO_COLUMN=1: AresQuerySetGeoColumn
+        on = os.environ.get("GEO_COLUMN", "0") == "1"
+        res += geo(be, dev, 1 << 24, 100, 20, geo_column=on) + geo(be, dev, 1 << 22, 250, 400, geo_column=on)
+    if "geoquery" in which:  # GEOQUERY_ROWS / GEOQUERY_BATCH_ROWS
+        res += geo_query_leg(be, dev, int(float(os.environ.get("GEOQUERY_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("GEOQUERY_BATCH_ROWS", str(1 << 26)))))
     for r in res: print(json.dumps(r), flush=True)
     os.makedirs("gpurun_out", exist_ok=True)
     json.dump(res, open("gpurun_out/bench_configs_%s.json" % "_".join(which), "w"), indent=1)
