@@ -1,4 +1,4 @@
-// Build-time check of the RCCL entry points ares_driver.cpp binds with dlsym under hand-declared signatures
+// Build-time check of the RCCL entry points shard_merge.cpp binds with dlsym under hand-declared signatures
 // (AresCommCreateRccl, rccl_all_gather, rccl_all_to_all): where <rccl/rccl.h> is installed, every declared signature is
 // compared with the header's — argument by argument, with the substitutions the binding makes (int for the 4-byte
 // result / datatype enums, void * for the opaque communicator and stream handles, a 128-byte struct for ncclUniqueId).

@@ -1,5 +1,5 @@
 """ctypes binding of libaresdriver.so — the C++ host side of the batch pipeline
-(aresdb_amd/csrc/host/ares_driver.cpp, a mirror of the reference's Go batch executor).
+(aresdb_amd/csrc/host/, a mirror of the reference's Go batch executor: batch_executor.cpp and its neighbours).
 
 `NativeQuery` has the same surface as executor.BatchContext/BatchExecutor/fetch_results, so tests
 run one plan through the Python mirror and the C++ driver and compare; bench.py uses the C++ driver
