@@ -180,6 +180,12 @@ class GeoShapeColumn(C.Structure):
                 ("inOrOut", C.c_int), ("out", C.c_void_p)]
 
 
+class LocalTimeColumn(C.Structure):
+    """AresLocalTimeColumn (include/ares_extensions.h): the query of AresLocalTimeColumnRun"""
+    _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("time", InputVector), ("join", FusedJoin),
+                ("zone", InputVector), ("outType", C.c_int), ("out", C.c_void_p)]
+
+
 # sizes pinned by include/ares_algorithm.h's static assertions (SURVEY.md 8b)
 ABI_SIZES = {CGoCallResHandle: 16, RecordID: 8, CuckooHashIndex: 40, DefaultValue: 24,
              VectorPartySlice: 56, ScratchSpaceVector: 16, ConstantVector: 24,
@@ -409,6 +415,29 @@ class Backend:
         self._algo.AresGeoShapeColumnStats.argtypes, self._algo.AresGeoShapeColumnStats.restype = [C.POINTER(C.c_ulonglong)], None
         self._algo.AresGeoShapeColumnStats(c)
         return {"batches": int(c[0]), "declined": int(c[1]), "rows": int(c[2]), "live": int(c[3]), "chunks": int(c[4])}
+
+    @property
+    def has_local_time_column(self):
+        return hasattr(self._algo, "AresLocalTimeColumnRun")
+
+    def local_time_column_run(self, query, batch_rows, stream=None, device=0):
+        """AresLocalTimeColumnRun: the slice of the local-time column (AresJoinColumnBytes(rows, Uint32) bytes at query.out);
+        the call does not wait for the stream (AresError, "not fusable: ..." among them, as every call)."""
+        fn = self._algo.AresLocalTimeColumnRun  # AttributeError: this library has no such entry point
+        fn.argtypes = [C.POINTER(LocalTimeColumn), C.c_int, C.POINTER(VectorPartySlice), _S, _I]
+        fn.restype = CGoCallResHandle
+        out = VectorPartySlice()
+        res = _check(fn(C.byref(query), int(batch_rows), C.byref(out), stream, device))
+        assert res == batch_rows
+        return out
+
+    def local_time_column_stats(self):
+        """{batches, declined, rows, probed, direct} of AresLocalTimeColumnRun since the process started: probed = 256 or 65536
+        per direct batch, the rows probed of a probe batch; the caller has waited for its streams."""
+        c = (C.c_ulonglong * 5)()
+        self._algo.AresLocalTimeColumnStats.argtypes, self._algo.AresLocalTimeColumnStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresLocalTimeColumnStats(c)
+        return {"batches": int(c[0]), "declined": int(c[1]), "rows": int(c[2]), "probed": int(c[3]), "direct": int(c[4])}
 
     def select_run_stats(self):
         """{rejected, staged}: tiles of AresFusedFilterSelect thrown away by one run of a run-length filter column, and tiles

@@ -189,10 +189,6 @@ int geo_column_grid(int64_t rows) {
   return capped_grid(tiles, 256 * 8);  // geo_intersect_kernel's: 8 workgroups per CU
 }
 
-size_t padded64(size_t bytes) { return (bytes + 63) / 64 * 64; }
-
-size_t bitmap_bytes(int rows) { return padded64((static_cast<size_t>(rows > 0 ? rows : 0) + 7) / 8); }
-
 int geo_shape_column(int device, const AresGeoShapeColumn &q, int batchRows, VectorPartySlice *outSlice, hipStream_t stream) {
   if (!geo_column_enabled()) throw NotFusable("switched off (ARES_GEO_COLUMN=0)");
   if (batchRows < 0) throw NotFusable("size");

@@ -121,11 +121,7 @@ int join_columns_grid(int64_t rows) {
   return capped_grid(blocks, 256 * 16);  // hash_lookup_kernel's
 }
 
-size_t padded64(size_t bytes) { return (bytes + 63) / 64 * 64; }
-
 bool joinable_type(int t) { return t == Int8 || t == Uint8 || t == Int16 || t == Uint16 || t == Int32 || t == Uint32 || t == Float32; }
-
-size_t bitmap_bytes(int rows) { return padded64((static_cast<size_t>(rows > 0 ? rows : 0) + 7) / 8); }
 
 int join_columns(int device, const AresJoinColumns &q, int batchRows, VectorPartySlice *outSlices, hipStream_t stream) {
   if (!join_columns_enabled()) throw NotFusable("switched off (ARES_JOIN_COLUMNS=0)");

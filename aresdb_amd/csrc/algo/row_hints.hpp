@@ -46,4 +46,8 @@ inline bool bind_hint(const AresFusedExpr &e, int batchRows, hipStream_t stream,
   return true;
 }
 
+// the layout of a row-space column: [validity bitmap][values], each padded to a multiple of 64 bytes
+inline size_t padded64(size_t bytes) { return (bytes + 63) / 64 * 64; }
+inline size_t bitmap_bytes(int rows) { return padded64((static_cast<size_t>(rows > 0 ? rows : 0) + 7) / 8); }
+
 }  // namespace ares

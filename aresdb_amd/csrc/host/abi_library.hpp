@@ -64,6 +64,7 @@ struct AbiLibrary {
   decltype(&::AresJoinColumnBytes) JoinColumnBytes = nullptr;              // ... the size of one of its outputs
   decltype(&::AresGeoShapeColumnRun) GeoShapeColumnRun = nullptr;          // optional extension, with ...
   decltype(&::AresGeoShapeColumnBytes) GeoShapeColumnBytes = nullptr;      // ... the size of its output
+  decltype(&::AresLocalTimeColumnRun) LocalTimeColumnRun = nullptr;        // optional extension (sized by JoinColumnBytes)
   decltype(&::Expand) Expand;
   // libmem
   decltype(&::DeviceAllocate) DeviceAllocate;
@@ -119,6 +120,7 @@ struct AbiLibrary {
     bind(algoHandle, "AresJoinColumnBytes", JoinColumnBytes, true);
     bind(algoHandle, "AresGeoShapeColumnRun", GeoShapeColumnRun, true);
     bind(algoHandle, "AresGeoShapeColumnBytes", GeoShapeColumnBytes, true);
+    bind(algoHandle, "AresLocalTimeColumnRun", LocalTimeColumnRun, true);
     bind(memHandle, "DeviceAllocate", DeviceAllocate);
     bind(memHandle, "DeviceFree", DeviceFree);
     bind(memHandle, "WaitForCudaStream", WaitForCudaStream);

@@ -81,6 +81,16 @@ typedef struct {
    * query, as before. */
   int isNonAggregation;
   int limit;
+  /* Local-time bucketing (query/time_bucketizer.go:72-92): `timezone: cities.timezone` compiles to
+   * FLOOR(CONVERT_TZ(request_at, cities.timezone), bucket), where CONVERT_TZ is the Plus functor and the joined enum column is
+   * read through the int16 offset table of prepareTimezoneTable (query/aql_processor.go:459-508).  timezoneLookup is that table
+   * on the device, convertTzNodes the ARES_NODE_BINARY nodes that are CONVERT_TZ: a foreign-column leaf that is a direct child
+   * of one is handed to the library with TimezoneLookup / TimezoneLookupSize, every other foreign leaf with NULL / 0
+   * (query/time_series_aggregate.go:506-516).  All four zero: no such node, as before. */
+  const int16_t *timezoneLookup;
+  int timezoneLookupSize;
+  const int *convertTzNodes;
+  int numConvertTzNodes;
 } AresQueryPlan;
 
 typedef struct AresQuery AresQuery; /* oopkBatchContext + executor of one query on one device */
@@ -131,7 +141,14 @@ void AresQuerySetLastBatch(AresQuery *q, int isLast);
  * the column-versus-constant shape as pruning hints) and runs the ordinary steps — the fused extension included — over the
  * rewritten plan and its columns + the joined ones, which are released with the batch's input columns.  A batch with base
  * counts takes the original plan; so does a batch the library declines ("not fusable"), after which the query stops asking.
- * Anything else — a non-aggregation query, a library without the entry point — is untouched. */
+ * Anything else — a non-aggregation query, a library without the entry point — is untouched.
+ * A CONVERT_TZ node (convertTzNodes) is one resolved leaf of its own — local time, AresLocalTimeColumnRun — when it is an inner
+ * node whose lhs is a bare main-table column and whose rhs is a foreign leaf of type Uint8 or Uint16, the plan has a timezoneLookup
+ * and the node's outType is Uint32 or Int32: the walk does not descend into it, and it becomes a main-table column of that type
+ * behind the batch's own columns and the joined ones; identical (time column, table, zone column, type) share one, at most two.
+ * A batch then issues one AresJoinColumnsRun per table that OTHER leaves read and one AresLocalTimeColumnRun per local time; a
+ * table only zone columns read gets neither HashLookup nor AresJoinColumnsRun.  A CONVERT_TZ node of any other shape — a root
+ * of a filter, dimension or measure among them — or a library without that entry point makes the query ineligible. */
 void AresQuerySetJoinColumns(AresQuery *q, int on);
 /* The geofence verdict resolved once per batch, in row space (off by default; AresGeoShapeColumnRun, include/ares_extensions.h).
  * Decided when it is set: an AGGREGATION query (HashReduce, Sort + Reduce or HyperLogLog) with a geo intersection whose points are

@@ -118,8 +118,9 @@ void AresQuery::releaseAll() {
 }
 
 // -- processExpression (time_series_aggregate.go:491-593) --
-// withRids = false: a joined column for an extension that has no record-id vectors
-IV AresQuery::columnInput(const AresPlanNode &n, bool withRids) {
+// withRids = false: a joined column for an extension that has no record-id vectors; withTimezone: the leaf is a direct child
+// of a CONVERT_TZ node and is read through the plan's offset table (time_series_aggregate.go:506-516)
+IV AresQuery::columnInput(const AresPlanNode &n, bool withRids, bool withTimezone) {
   IV iv;
   if (n.table == 0) {
     if (n.column < 0 || n.column >= numColumns) throw AbiError("column index out of range");
@@ -136,7 +137,10 @@ IV AresQuery::columnInput(const AresPlanNode &n, bool withRids) {
   f.BaseBatchID = ft.t.baseBatchID;
   f.NumBatches = ft.t.numBatches;
   f.NumRecordsInLastBatch = ft.t.numRecordsInLastBatch;
-  f.TimezoneLookupSize = 0;  // TimezoneLookup stays NULL (zeroed box)
+  if (withTimezone) {  // (otherwise TimezoneLookup stays NULL and its size 0: the zeroed box)
+    *const_cast<int16_t **>(&f.TimezoneLookup) = const_cast<int16_t *>(plan.timezoneLookup);
+    f.TimezoneLookupSize = static_cast<int16_t>(plan.timezoneLookupSize);
+  }
   f.DataType = static_cast<DataType>(ft.dataTypes[n.column]);
   iv->Type = ForeignColumnInput;
   return iv;
@@ -213,14 +217,14 @@ void AresQuery::runAction(const Action &a, int functor, IV *in, int arity) {
 
 // returns the node's value as an InputVector (leaf or scratch frame) when action is NONE,
 // otherwise performs the root action
-IV AresQuery::processExpression(int nodeIdx, const Action &action) {
+IV AresQuery::processExpression(int nodeIdx, const Action &action, bool underConvertTz) {
   const AresPlanNode &n = batchPlan->nodes.at(nodeIdx);
   IV none;
   switch (n.kind) {
     case ARES_NODE_COLUMN:
     case ARES_NODE_CONST_INT:
     case ARES_NODE_CONST_FLOAT: {
-      IV iv = n.kind == ARES_NODE_COLUMN ? columnInput(n) : constantInput(n);
+      IV iv = n.kind == ARES_NODE_COLUMN ? columnInput(n, true, underConvertTz) : constantInput(n);
       if (action.kind != Action::NONE) {
         runAction(action, Noop, &iv, 1);
         return none;
@@ -243,8 +247,9 @@ IV AresQuery::processExpression(int nodeIdx, const Action &action) {
     }
     case ARES_NODE_BINARY: {
       IV in[2];
-      in[0] = processExpression(n.lhs, Action());
-      in[1] = processExpression(n.rhs, Action());
+      const bool convertTz = batchPlan->isConvertTz(nodeIdx);
+      in[0] = processExpression(n.lhs, Action(), convertTz);
+      in[1] = processExpression(n.rhs, Action(), convertTz);
       if (action.kind != Action::NONE) {
         runAction(action, n.op, in, 2);
         return none;

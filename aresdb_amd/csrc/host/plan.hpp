@@ -50,6 +50,12 @@ struct Plan {
   std::vector<Foreign> foreign;
   bool hasGeo = false;
   AresGeoIntersection geo;
+  // local-time bucketing: the int16 offset table on the device and, per node, whether it is a CONVERT_TZ node — the foreign
+  // leaves directly below one are read through the table (query/time_series_aggregate.go:506-516)
+  const int16_t *timezoneLookup = nullptr;
+  int timezoneLookupSize = 0;
+  std::vector<char> convertTz;
+  bool isConvertTz(int node) const { return node >= 0 && node < static_cast<int>(convertTz.size()) && convertTz[node]; }
 
   explicit Plan(const AresQueryPlan &p)
       : nodes(p.nodes, p.nodes + p.numNodes), filters(p.filters, p.filters + p.numFilters),
@@ -69,6 +75,14 @@ struct Plan {
     if (p.geo) {
       hasGeo = true;
       geo = *p.geo;
+    }
+    timezoneLookup = p.timezoneLookup;
+    timezoneLookupSize = p.timezoneLookupSize;
+    convertTz.assign(nodes.size(), 0);
+    for (int i = 0; i < p.numConvertTzNodes; i++) {
+      const int node = p.convertTzNodes[i];
+      if (node < 0 || node >= p.numNodes || nodes[node].kind != ARES_NODE_BINARY) throw AbiError("a CONVERT_TZ node must be a binary node");
+      convertTz[node] = 1;
     }
   }
   int measureBytes() const { return data_type_bytes(measureType); }

@@ -27,6 +27,18 @@ struct RowSpace {
     int first = 0;             // position of columns[0] among the added columns
   };
   std::vector<JoinedTable> tables;  // JOIN_COLUMNS: one per foreign table
+  // JOIN_COLUMNS: the local-time columns (AresLocalTimeColumnRun), behind the joined ones: one per distinct
+  // (time column, table, zone column, type) the query's CONVERT_TZ nodes name, at most two
+  struct LocalTime {
+    int timeColumn;  // main table
+    int table;       // foreign table, from 0
+    int zoneColumn;  // column of that table
+    int outType;     // the CONVERT_TZ nodes' outType: the column's DataType
+    bool operator==(const LocalTime &o) const {
+      return timeColumn == o.timeColumn && table == o.table && zoneColumn == o.zoneColumn && outType == o.outType;
+    }
+  };
+  std::vector<LocalTime> localTimes;
   RowSpace(Kind k, const Plan &original) : kind(k), plan(original) {}
 };
 
@@ -131,9 +143,9 @@ struct AresQuery {
     int64_t valueOff = 0, nullOff = 0;
     int prevResultSize = 0;
   };
-  IV columnInput(const AresPlanNode &n, bool withRids = true);
+  IV columnInput(const AresPlanNode &n, bool withRids = true, bool withTimezone = false);
   void runAction(const Action &a, int functor, IV *in, int arity);
-  IV processExpression(int nodeIdx, const Action &action);
+  IV processExpression(int nodeIdx, const Action &action, bool underConvertTz = false);
 
   // BatchExecutorImpl.Run (aql_batchexecutor.go:103-273)
   void preExec();
@@ -167,6 +179,7 @@ struct AresQuery {
   void setRowSpace(ares_host::RowSpace::Kind kind, bool on);
   int pruningHints(AresFusedExpr *out);
   bool runJoinColumns(ares_host::RowSpace &rs, int n);
+  bool runLocalTimeColumns(ares_host::RowSpace &rs, int n);
   bool runGeoColumn(int n);
   bool resolve(const VectorPartySlice *cols, int ncols, int n);
 };

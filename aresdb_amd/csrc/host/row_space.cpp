@@ -1,6 +1,6 @@
 // Row-space rewrites: columns an extension resolves once per batch, behind the batch's own, and the plan that reads them.  The
 // Go host has no counterpart; the contracts are at AresQuerySetJoinColumns / AresQuerySetGeoColumn (ares_driver.h) and at
-// AresJoinColumnsRun / AresGeoShapeColumnRun (include/ares_extensions.h).
+// AresJoinColumnsRun / AresLocalTimeColumnRun / AresGeoShapeColumnRun (include/ares_extensions.h).
 //
 // A query holds at most one rewrite — joined columns need foreign tables, the geo column needs none — and both follow one
 // protocol per batch (resolve): they differ in their once-per-query planner and in the body that fills the extension's query
@@ -16,30 +16,64 @@ namespace {
 // Joined columns: an aggregation query whose foreign references are all leaf columns of 1-, 2- or 4-byte non-Bool types gets the
 // plan with every such leaf turned into a main-table column, the foreign filters appended to the main filters and no foreign
 // tables.  Null: not eligible.
+//
+// A CONVERT_TZ node (Plan::convertTz) is one resolved leaf of its own, local time: eligible when it is an inner node whose lhs is
+// a bare main-table column and whose rhs is a foreign leaf of type Uint8 or Uint16, the plan has an offset table and the node's
+// outType — the type of the scratch vector it would fill — is Uint32 or Int32.  The walk does not descend into it, so a table
+// that only zone columns read has no joined column; the node becomes a main-table column behind the joined ones, identical
+// (time column, table, zone column, type) sharing one.  Any other CONVERT_TZ node — a root, whose result type the operands'
+// types decide, among them — or more than two distinct local times: not eligible.
 std::unique_ptr<RowSpace> plan_joined_columns(const Plan &plan, const AbiLibrary &lib) {
   if (plan.isNonAggregation || plan.foreign.empty() || !lib.JoinColumnsRun || !lib.JoinColumnBytes) return nullptr;
   if (plan.hasGeo && plan.geo.pointTable != 0) return nullptr;  // a geo point from a foreign table
   const int numNodes = static_cast<int>(plan.nodes.size());
   std::vector<char> reached(plan.nodes.size(), 0);
+  std::vector<RowSpace::LocalTime> localTimes;
+  std::vector<std::pair<int, size_t>> localTimeNodes;  // (node, position inside localTimes)
   bool ok = true;
+  // the local time a CONVERT_TZ node stands for; false: no eligible shape
+  auto local_time = [&](const AresPlanNode &n, bool isRoot, RowSpace::LocalTime *lt) {
+    if (isRoot || !lib.LocalTimeColumnRun || !plan.timezoneLookup) return false;
+    if (n.outType != Uint32 && n.outType != Int32) return false;
+    if (n.lhs < 0 || n.lhs >= numNodes || n.rhs < 0 || n.rhs >= numNodes) return false;
+    const AresPlanNode &time = plan.nodes[n.lhs], &zone = plan.nodes[n.rhs];
+    if (time.kind != ARES_NODE_COLUMN || time.table != 0 || zone.kind != ARES_NODE_COLUMN) return false;
+    if (zone.table < 1 || zone.table > static_cast<int>(plan.foreign.size())) return false;
+    const Plan::Foreign &ft = plan.foreign[zone.table - 1];
+    if (zone.column < 0 || zone.column >= ft.t.numColumns) return false;
+    if (ft.dataTypes[zone.column] != Uint8 && ft.dataTypes[zone.column] != Uint16) return false;
+    *lt = RowSpace::LocalTime{time.column, zone.table - 1, zone.column, n.outType};
+    return true;
+  };
   // marks what `root` reaches; a foreign leaf below a main-table filter makes the query ineligible
-  auto walk = [&](int root, bool foreignAllowed, auto &&self) -> void {
+  auto walk = [&](int root, bool foreignAllowed, bool isRoot, auto &&self) -> void {
     if (root < 0 || root >= numNodes) {
       ok = false;
       return;
     }
     const AresPlanNode &n = plan.nodes[root];
     reached[root] = 1;
+    if (plan.isConvertTz(root)) {
+      RowSpace::LocalTime lt;
+      if (!foreignAllowed || !local_time(n, isRoot, &lt)) {
+        ok = false;
+        return;
+      }
+      const size_t at = std::find(localTimes.begin(), localTimes.end(), lt) - localTimes.begin();
+      if (at == localTimes.size()) localTimes.push_back(lt);
+      localTimeNodes.emplace_back(root, at);
+      return;
+    }
     if (n.kind == ARES_NODE_COLUMN && n.table != 0 && !foreignAllowed) ok = false;
-    if (n.kind == ARES_NODE_UNARY || n.kind == ARES_NODE_BINARY) self(n.lhs, foreignAllowed, self);
-    if (n.kind == ARES_NODE_BINARY) self(n.rhs, foreignAllowed, self);
+    if (n.kind == ARES_NODE_UNARY || n.kind == ARES_NODE_BINARY) self(n.lhs, foreignAllowed, false, self);
+    if (n.kind == ARES_NODE_BINARY) self(n.rhs, foreignAllowed, false, self);
   };
-  for (int f : plan.filters) walk(f, false, walk);
-  for (int f : plan.foreignFilters) walk(f, true, walk);
+  for (int f : plan.filters) walk(f, false, true, walk);
+  for (int f : plan.foreignFilters) walk(f, true, true, walk);
   for (size_t i = 0; i < plan.dimNodes.size(); i++)
-    if (!(plan.hasGeo && plan.geo.dimIndex == static_cast<int>(i))) walk(plan.dimNodes[i], true, walk);
-  walk(plan.measureNode, true, walk);
-  if (!ok) return nullptr;
+    if (!(plan.hasGeo && plan.geo.dimIndex == static_cast<int>(i))) walk(plan.dimNodes[i], true, true, walk);
+  walk(plan.measureNode, true, true, walk);
+  if (!ok || localTimes.size() > 2) return nullptr;
   std::unique_ptr<RowSpace> rs(new RowSpace(RowSpace::JOIN_COLUMNS, plan));
   rs->tables.assign(plan.foreign.size(), RowSpace::JoinedTable());
   std::vector<std::pair<int, size_t>> leaves;  // (node, position inside its table's list)
@@ -66,6 +100,13 @@ std::unique_ptr<RowSpace> plan_joined_columns(const Plan &plan, const AbiLibrary
     rs->leaves.emplace_back(leaf.first, rs->tables[n.table - 1].first + static_cast<int>(leaf.second));
     n.table = 0;  // (its column is the batch's column count + the position: set per batch)
   }
+  for (const auto &node : localTimeNodes) {
+    rs->plan.nodes[node.first] = main_column(0);
+    rs->plan.convertTz[node.first] = 0;
+    rs->leaves.emplace_back(node.first, rs->numAdded + static_cast<int>(node.second));
+  }
+  rs->localTimes = localTimes;
+  rs->numAdded += static_cast<int>(localTimes.size());
   rs->plan.filters.insert(rs->plan.filters.end(), plan.foreignFilters.begin(), plan.foreignFilters.end());
   rs->plan.foreignFilters.clear();
   rs->plan.foreign.clear();
@@ -147,6 +188,32 @@ bool AresQuery::runJoinColumns(RowSpace &rs, int n) {
     }
     calls++;
     CGoCallResHandle h = lib->JoinColumnsRun(&q.get(), n, &extendedColumns[static_cast<size_t>(numColumns + jt.first)], stream, device);
+    if (declined(h)) return false;
+    check(h);
+  }
+  return runLocalTimeColumns(rs, n);
+}
+
+// One AresLocalTimeColumnRun per local time of the query, into fresh allocations behind the joined columns.  false: the library
+// declines the shape.
+bool AresQuery::runLocalTimeColumns(RowSpace &rs, int n) {
+  const int first = rs.numAdded - static_cast<int>(rs.localTimes.size());
+  for (size_t k = 0; k < rs.localTimes.size(); k++) {
+    const RowSpace::LocalTime &lt = rs.localTimes[k];
+    const Plan::Foreign &ft = plan.foreign[lt.table];
+    Pod<AresLocalTimeColumn> q;
+    q->numFilters = pruningHints(q->filters);
+    memcpy(&q->time, &columnInput(main_column(lt.timeColumn)).get(), sizeof(InputVector));
+    memcpy(&q->join.key, &columnInput(main_column(ft.t.joinColumn)).get(), sizeof(InputVector));
+    memcpy(&q->join.index, &ft.t.index, sizeof(CuckooHashIndex));
+    AresPlanNode zone = main_column(lt.zoneColumn);
+    zone.table = lt.table + 1;
+    memcpy(&q->zone, &columnInput(zone, false, true).get(), sizeof(InputVector));
+    q->outType = static_cast<DataType>(lt.outType);
+    joinedOutputs.push_back(alloc(lib->JoinColumnBytes(n, Uint32)));
+    q->out = static_cast<uint8_t *>(joinedOutputs.back());
+    calls++;
+    CGoCallResHandle h = lib->LocalTimeColumnRun(&q.get(), n, &extendedColumns[static_cast<size_t>(numColumns + first) + k], stream, device);
     if (declined(h)) return false;
     check(h);
   }

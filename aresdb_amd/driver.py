@@ -42,7 +42,9 @@ class QueryPlanC(C.Structure):
                 ("useHashReduction", C.c_int),
                 ("foreignTables", C.POINTER(ForeignTableC)), ("numForeignTables", C.c_int),
                 ("useFusedExtension", C.c_int), ("geo", C.POINTER(GeoIntersectionC)),
-                ("isNonAggregation", C.c_int), ("limit", C.c_int)]
+                ("isNonAggregation", C.c_int), ("limit", C.c_int),
+                ("timezoneLookup", C.c_void_p), ("timezoneLookupSize", C.c_int),
+                ("convertTzNodes", C.POINTER(C.c_int)), ("numConvertTzNodes", C.c_int)]
 
 
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
@@ -138,6 +140,7 @@ class NativeQuery:
         self.foreign_column_names = foreign_column_names or [sorted(ft.batches) for ft in plan.foreign_tables]
         self._keep = []
         nodes = []
+        convert_tz = []  # the Binary nodes that are CONVERT_TZ
 
         def emit(e):
             n = PlanNode()
@@ -159,6 +162,8 @@ class NativeQuery:
             else:
                 raise TypeError(f"unsupported expression node {e!r}")
             nodes.append(n)
+            if isinstance(e, Binary) and e.convert_tz:
+                convert_tz.append(len(nodes) - 1)
             return len(nodes) - 1
 
         filters = [emit(f) for f in plan.filters]
@@ -196,6 +201,10 @@ class NativeQuery:
         pc.useFusedExtension = int(getattr(plan, "use_fused_extension", False))
         pc.isNonAggregation = int(getattr(plan, "is_non_aggregation", False))
         pc.limit = int(getattr(plan, "limit", -1))
+        if convert_tz:
+            pc.timezoneLookup = getattr(plan, "timezone_lookup", None)
+            pc.timezoneLookupSize = int(getattr(plan, "timezone_lookup_size", 0))
+            pc.convertTzNodes, pc.numConvertTzNodes = arr(C.c_int, convert_tz), len(convert_tz)
         geo = getattr(plan, "geo", None)
         if geo is not None:
             g = GeoIntersectionC()

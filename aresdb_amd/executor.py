@@ -48,6 +48,9 @@ class Binary:
     lhs: object
     rhs: object
     out_type: int = abi.Int32
+    # CONVERT_TZ (op = Plus, query/time_bucketizer.go:72-92): a foreign column directly below is read through the plan's
+    # time-zone offset table (query/time_series_aggregate.go:506-516)
+    convert_tz: bool = False
 
 
 @dataclass
@@ -99,6 +102,10 @@ class QueryPlan:
     # literal, query/aql_compiler.go:1147-1153): run as query/aql_nonaggr_batchexecutor.go does; limit < 0: none.
     is_non_aggregation: bool = False
     limit: int = -1
+    # prepareTimezoneTable (query/aql_processor.go:459-508): device pointer of the int16 offset per time-zone enum value, and
+    # the number of entries; read by the foreign leaves directly below a Binary with convert_tz
+    timezone_lookup: Optional[int] = None
+    timezone_lookup_size: int = 0
 
     @property
     def measure_bytes(self):
@@ -329,7 +336,7 @@ class BatchContext:
         self.hll_vector = self.hll_dim_reg_count = 0
 
     # -- processExpression (time_series_aggregate.go:491-593) ---------------------------------------
-    def _foreign_input(self, e: Col):
+    def _foreign_input(self, e: Col, with_timezone=False):
         ft = self.plan.foreign_tables[e.table - 1]
         slices = ft.batches[e.name]
         arr = (abi.VectorPartySlice * len(slices))(*slices)
@@ -341,14 +348,18 @@ class BatchContext:
         f.BaseBatchID = ft.base_batch_id
         f.NumBatches = len(slices)
         f.NumRecordsInLastBatch = ft.num_records_in_last_batch
-        f.TimezoneLookup, f.TimezoneLookupSize = None, 0
+        if with_timezone:  # time_series_aggregate.go:506-516
+            f.TimezoneLookup, f.TimezoneLookupSize = self.plan.timezone_lookup, self.plan.timezone_lookup_size
+        else:
+            f.TimezoneLookup, f.TimezoneLookupSize = None, 0
         f.DataType = ft.data_types[e.name]
         iv.Type = abi.ForeignColumnInput
         return iv
 
-    def process_expression(self, e, action):
+    def process_expression(self, e, action, parent=None):
         if isinstance(e, Col):
-            iv = column_input(self.columns[e.name]) if e.table == 0 else self._foreign_input(e)
+            iv = column_input(self.columns[e.name]) if e.table == 0 else \
+                self._foreign_input(e, isinstance(parent, Binary) and parent.convert_tz)
             if action:
                 action(abi.Noop, [iv])
                 return None
@@ -360,7 +371,7 @@ class BatchContext:
                 return None
             return iv
         if isinstance(e, Unary):
-            iv = self.process_expression(e.arg, None)
+            iv = self.process_expression(e.arg, None, e)
             if action:
                 action(e.op, [iv])
                 return None
@@ -376,8 +387,8 @@ class BatchContext:
                 self.shrink_stack_frame()
             return self._scratch_input(values, nulls_off, e.out_type)
         if isinstance(e, Binary):
-            lhs = self.process_expression(e.lhs, None)
-            rhs = self.process_expression(e.rhs, None)
+            lhs = self.process_expression(e.lhs, None, e)
+            rhs = self.process_expression(e.rhs, None, e)
             if action:
                 action(e.op, [lhs, rhs])
                 return None

@@ -166,10 +166,11 @@ def archive_batch(cols, valid, key):
     return cols, valid, {key: np.concatenate([starts, [len(v)]]).astype(np.uint32)}
 
 
-def stash_table(be, attr, attr_valid, join_column, num_last):
+def stash_table(be, attr, attr_valid, join_column, num_last, zone=None):
     """A dimension table of at most four keys 0, 1, ... without any hashing: a cuckoo index with numHashes = 0 whose entries
     all lie in the stash (memstore/cuckoo_index.go layout: [RecordID x8][signature x8][key x8] per bucket, the stash behind
-    the numBuckets buckets).  Key i -> record (batch 1, index i) of the one-batch column "attr".  (ForeignTable, what to free)"""
+    the numBuckets buckets).  Key i -> record (batch 1, index i) of the one-batch column "attr" and, when given, of the Uint8
+    time-zone enum column "zone".  (ForeignTable, what to free)"""
     from .executor import ForeignTable
     keys = len(attr)
     assert keys <= 4  # HASH_STASH_SIZE
@@ -186,7 +187,11 @@ def stash_table(be, attr, attr_valid, join_column, num_last):
     idx.keyBytes, idx.numHashes, idx.numBuckets = 4, 0, 1
     ft = ForeignTable(join_column=join_column, index=idx, batches={"attr": [column.vp]}, data_types={"attr": abi.Uint32},
                       base_batch_id=1, num_records_in_last_batch=num_last)
-    return ft, [index_buf, column]
+    keep = [index_buf, column]
+    if zone is not None:
+        keep.append(DeviceColumn(be, abi.Uint8, zone))
+        ft.batches["zone"], ft.data_types["zone"] = [keep[-1].vp], abi.Uint8
+    return ft, keep
 
 
 def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
@@ -233,6 +238,24 @@ def run_smoke(hip, oracle, n=20000, batches=3, seed=7):
         assert len(per_node) > 100, len(per_node)
         compare_results(resolved, per_node)
     for d in keep:
+        d.free()
+    # one tiny time-zone query — group by the hour in the joined zone's local time, FLOOR(CONVERT_TZ(ts, zone), 3600), and
+    # SUM(m) — both ways through the C++ driver: the per-node sequence (HashLookup, Plus through the offset table into scratch,
+    # Floor), and local time resolved once per batch in row space (AresLocalTimeColumnRun) with Floor over that column
+    ft, keep = stash_table(hip, np.array([10, 20, 600, 30]), None, "d2", 4, zone=np.array([2, 0, 1, 9]))
+    offsets = DeviceColumn(hip, abi.Int16, np.array([-18000, 19800, 3600], np.int16))  # (enum 9 lies past the table: offset 0)
+    local_hour = Binary(abi.Floor, Binary(abi.Plus, Col("ts"), Col("zone", table=1), out_type=abi.Uint32, convert_tz=True), Const(3600))
+    plan = QueryPlan(filters=filters, foreign_tables=[ft], dimensions=[DimensionSpec(local_hour, abi.Uint32), DimensionSpec(Col("d2"), abi.Uint32)],
+                     measure=Col("m"), agg=abi.AGGR_SUM_FLOAT, measure_type=abi.Float64, use_hash_reduction=True,
+                     timezone_lookup=offsets.vp.BasePtr, timezone_lookup_size=3)
+    before = hip.local_time_column_stats()
+    per_node, _ = run_query_native(hip, plan, data)
+    assert hip.local_time_column_stats() == before
+    resolved, _ = run_query_native(hip, plan, data, join_columns=True)
+    assert hip.local_time_column_stats()["batches"] - before["batches"] == batches
+    assert len(per_node) > 100, len(per_node)
+    compare_results(resolved, per_node)
+    for d in keep + [offsets]:
         d.free()
     # the last queries' shapes may still be compiling on the background thread: a process must not run into its exit handlers
     # with a compilation in flight (the compiler's own statics are torn down under it)

@@ -362,6 +362,56 @@ CGoCallResHandle AresGeoShapeColumnRun(const AresGeoShapeColumn *q, int batchRow
  * counted on the device: the caller has waited for its streams */
 void AresGeoShapeColumnStats(unsigned long long *counters);
 
+/* Local time resolved once per batch, in row space: for an AGGREGATION query that buckets a time column in the time zone of a
+ * joined table — FLOOR(CONVERT_TZ(request_at, cities.timezone), bucket), query/time_bucketizer.go:72-92, where CONVERT_TZ is
+ * Plus and the joined enum column is read through the int16 offset table (TimezoneLookup, query/iterator.hpp:888-914).  Local
+ * time is a pure function of (time, join key): it is written as an ordinary mode-2 main-table column of the batch's length, and
+ * the host then runs the batch with `Floor(that column, bucket)` — the "one column (op constant)" shape of every fast path.  It
+ * replaces, for one batch without base counts and one (time column, table, zone column),
+ *   HashLookup over the survivors, then BinaryTransform(Plus, time, the zone column with its TimezoneLookup) into scratch.
+ * Output: AresJoinColumnsRun's layout, [bitmap: ceil(rows / 8) bytes, padded to a multiple of 64][values: rows x 4, padded to
+ * 64] at `out`, AresJoinColumnBytes(batchRows, Uint32) bytes in all, and
+ *   *outSlice = {BasePtr = out, NullsOffset = 0, ValuesOffset = the padded bitmap bytes, StartingIndex = 0,
+ *                Length = batchRows, DataType = outType}.
+ * Bitmap bits at or past batchRows inside the last written 8-byte word are 0; bytes past that word are not written.
+ * Row r is what the per-node sequence leaves for it: value = time[r] + offset taken mod 2^32, valid = time valid AND key valid
+ * AND record found AND joined value valid; a null row is written as value 0.  `offset` is what a foreign operand with a
+ * TimezoneLookup reads: tz[enum] for enum < TimezoneLookupSize, else 0; a mode-0 batch yields its default WITHOUT the lookup
+ * (query/iterator.hpp:922-926) and the default's validity; a null or missing key, a batch outside the table and an index at or
+ * past NumRecordsInLastBatch in the last batch give (0, null).
+ * Two flavours, byte-identical on every row that no hint prunes:
+ *   direct — the key column's type is 1 or 2 bytes wide (Int8, Uint8, Int16, Uint16).  A first kernel enumerates all 2^8 or
+ *     2^16 stored key values, widens each as HashLookup does (the column's type decides sign extension, keyBytes what is kept),
+ *     probes once per value and writes an (offset, valid) table of 4 bytes per value — at most 256 KiB — into a stream temporary;
+ *     a second kernel streams over the rows: time and key in, one gather from the table, the value out.  No probe per row; hints
+ *     are not evaluated.  Chosen when the key is narrow and batchRows >= the number of key values.
+ *   probe — every other key HashLookup accepts (4-byte types, Int64, UUID): AresJoinColumnsRun's geometry, one row and one
+ *     probe per lane.  filters are pruning HINTS exactly as AresJoinColumns::filters: a row that fails an evaluated hint is not
+ *     probed and gets (0, null); a hint the kernel cannot evaluate is ignored.
+ * Declined ("not fusable", nothing launched, nothing written): a null TimezoneLookup, a zone type other than Uint8 or Uint16 or
+ * a zone that is no ForeignColumnInput, a time type other than Uint32 or Int32 (outType likewise), a mode-0 or run-length time
+ * or key column or one shorter than batchRows, index geometry HashLookup rejects, a null or misaligned `out`,
+ * ARES_LOCAL_TIME=0.
+ * res = batchRows.  The call does not wait for the stream; the output is reported to libmem.so as written (AresMemNoteWrite).
+ * Environment (both obey AresReloadEnv): ARES_LOCAL_TIME=0 declines always, =probe / =direct (tests) force a flavour where it
+ * is applicable; ARES_LOCAL_TIME_GRID=n (tests) sets the number of workgroups. */
+typedef struct {
+  int numFilters;
+  AresFusedExpr filters[4]; /* pruning hints, as AresJoinColumns::filters (probe flavour only) */
+  InputVector time;         /* VectorPartyInput, main table, Uint32 or Int32, mode 1 or 2 */
+  AresFusedJoin join;       /* key column + cuckoo index of the zone's table */
+  InputVector zone;         /* ForeignColumnInput, Uint8 or Uint16, TimezoneLookup != NULL, RecordIDs ignored */
+  enum DataType outType;    /* Uint32 or Int32: the CONVERT_TZ node's outType; same bits either way */
+  uint8_t *out;             /* device, 64-byte aligned, AresJoinColumnBytes(batchRows, Uint32) bytes */
+} AresLocalTimeColumn;
+
+CGoCallResHandle AresLocalTimeColumnRun(const AresLocalTimeColumn *q, int batchRows, VectorPartySlice *outSlice, void *cudaStream,
+                                        int device);
+/* {batches run, batches declined, rows, keys probed, direct batches} since process start; keys probed = 256 or 65536 for a
+ * direct batch, for a probe batch the rows that passed every evaluated hint and had a valid key, counted on the device: the
+ * caller has waited for its streams */
+void AresLocalTimeColumnStats(unsigned long long *counters);
+
 #ifdef __cplusplus
 }
 #endif

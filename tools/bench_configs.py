@@ -441,6 +441,96 @@ def join_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, table_keys=(4000, 5
     return out
 
 
+def tz_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, nkeys=4000, zones=400):
+    """tzagg: trips per hour in each city's local time — the trips query (two time filters plus status) joined on city_id
+    (Uint16) to joinagg's 4 000-key table given a Uint8 zone column and a 400-entry offset table, grouped by
+    FLOOR(CONVERT_TZ(request_at, zone), 3600) and city_id: SUM(fare) through HashReduce and COUNT(*) through Sort + Reduce, each
+    through the per-node sequence (setter off), with AresQuerySetJoinColumns (the direct flavour of AresLocalTimeColumnRun: the
+    batches have more rows than the key has values) and with it under ARES_LOCAL_TIME=probe, on one build; results compared key
+    by key.  One JSON row per (query, path): wall ms per step, the per-kernel split and the keys probed in row space."""
+    import harness as H
+    from aresdb_amd import trips
+    from aresdb_amd.executor import Binary, Const
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(12)
+    batches = trips.trips_shard(rows, batch_rows, seed=11, device=dev)
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    ft, join_column, tb, dcols = _trips_join_table(be, dev, batches, nkeys, gen)
+    rng = np.random.default_rng(8)
+    zone = H.Column(be, abi.Uint8, rng.integers(0, 256, nkeys).astype(np.uint8))
+    ft.batches["zone"], ft.data_types["zone"] = [zone.vp], abi.Uint8
+    offsets = H.Buf(be, (rng.integers(-48, 57, zones) * 900).astype(np.int16))
+    names = list(batches[0].keys())
+    vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+    out = []
+    for count in (False, True):
+        first = None
+        for path in ("per-node", "direct", "probe"):
+            plan = trips.trips_plan(count=count)
+            local = Binary(abi.Plus, Col("request_at"), Col("zone", table=1), out_type=abi.Uint32, convert_tz=True)
+            plan.dimensions[0] = DimensionSpec(Binary(abi.Floor, local, Const(3600)), abi.Uint32)
+            plan.foreign_tables = [ft]
+            plan.timezone_lookup, plan.timezone_lookup_size = offsets.ptr, zones
+            if path == "probe":
+                os.environ["ARES_LOCAL_TIME"] = "probe"
+            else:
+                os.environ.pop("ARES_LOCAL_TIME", None)
+            be.reload_env()
+            packed = None
+            def run():
+                nonlocal packed
+                q = NativeQuery(be, plan, names, streams=streams)
+                q.set_join_columns(path != "per-node")
+                if packed is None:
+                    packed = q.pack_batches(vps)
+                q.run_batches(packed)
+                return q
+            compiles = -1
+            for _ in range(4):  # priming passes: the shape's kernels are compiled in the background
+                run().release()
+                state = be.rtc_wait()
+                if state is None or state["compiles"] == compiles:
+                    break
+                compiles = state["compiles"]
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            for _ in range(steps):
+                run().release()
+            torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+            be.profiler_enable(True)
+            stats0 = be.local_time_column_stats()
+            q = run(); torch.cuda.synchronize()
+            kernels = be.profiler_report(); be.profiler_enable(False)
+            stats1 = be.local_time_column_stats()
+            n, calls = q.result_size, q.calls
+            dims, valids, meas = q.fetch()
+            q.release()
+            values = meas.view(np.uint32 if count else np.float64)
+            keyed = np.stack([dims[0].view(np.uint32), dims[1].view(np.uint16).astype(np.uint32), valids[0].astype(np.uint32),
+                              valids[1].astype(np.uint32)], axis=1)
+            result = {tuple(k): v for k, v in zip(keyed.tolist(), values.tolist())}
+            check = "first"
+            if first is None:
+                first = result
+            elif result == first:
+                check = "ok"
+            else:  # (HashReduce groups by a 32-bit hash: which of two colliding rows represents their group depends on the path)
+                differing = len(set(result.items()) ^ set(first.items()))
+                check = "%d (key, value) pairs differ; totals %s" % (differing, "equal" if sum(result.values()) == sum(first.values()) else "DIFFER")
+            kernel_ms = sum(ms for c, ms in kernels.values())
+            out.append({"config": "tzagg", "table_keys": nkeys, "zones": zones, "query": "COUNT(*) via Sort+Reduce" if count else "SUM(fare) via HashReduce",
+                        "path": path, "rows": rows, "batches": len(vps), "batch_rows": batch_rows, "groups": n, "abi_calls": calls, "check": check,
+                        "local_time_batches": stats1["batches"] - stats0["batches"], "direct_batches": stats1["direct"] - stats0["direct"],
+                        "keys_probed_in_row_space": stats1["probed"] - stats0["probed"], "ms_per_step": dt * 1e3,
+                        "ms_per_1B_rows": dt * 1e3 * 1e9 / rows, "kernel_ms_per_step": kernel_ms, "kernel_ms_per_1B_rows": kernel_ms * 1e9 / rows,
+                        "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
+            print(json.dumps(out[-1]), flush=True)
+    os.environ.pop("ARES_LOCAL_TIME", None)
+    be.reload_env()
+    for c in [tb, zone, offsets] + dcols:
+        c.free()
+    return out
+
+
 def select_join_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1), table_keys=(4000, 50_000_000)):
     """select_leg's query with a join: the trips select plus one 4-byte attribute of a dimension table, selected, once with a
     foreign filter on it (attr < 500 of 0..999) and once without; limits 100, 1 M and none; through the ordinary sequence
@@ -1011,6 +1101,8 @@ def main():
     if "joinagg" in which:  # JOINAGG_ROWS / JOINAGG_BATCH_ROWS; JOINAGG_KEYS: the table sizes, comma separated
         res += join_agg_leg(be, dev, int(float(os.environ.get("JOINAGG_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("JOINAGG_BATCH_ROWS", str(1 << 26)))),
                             table_keys=tuple(int(float(x)) for x in os.environ.get("JOINAGG_KEYS", "4000,5e7").split(",")))
+    if "tzagg" in which:  # TZAGG_ROWS / TZAGG_BATCH_ROWS
+        res += tz_agg_leg(be, dev, int(float(os.environ.get("TZAGG_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("TZAGG_BATCH_ROWS", str(1 << 26)))))
     if "selectarchive" in which:  # the same switches as "select"
         res += select_archive_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                                   limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))
