@@ -145,6 +145,12 @@ class FusedExpr(C.Structure):
                 ("outType", C.c_int)]
 
 
+class FusedQuery(C.Structure):
+    """AresFusedQuery (include/ares_extensions.h): the query of AresFusedFilterHashReduce and of AresHintFusedBatch"""
+    _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("numDims", C.c_int), ("dims", FusedExpr * 4),
+                ("measure", FusedExpr), ("aggFunc", C.c_int)]
+
+
 class FusedSelect(C.Structure):
     """AresFusedSelect (include/ares_extensions.h): the query of AresFusedFilterSelect"""
     _fields_ = [("numFilters", C.c_int), ("filters", FusedExpr * 4), ("numDims", C.c_int),
@@ -321,6 +327,26 @@ class Backend:
 
     def flags(self):
         return self._mem.GetFlags()
+
+    @property
+    def has_scan_at_filter(self):
+        return hasattr(self._algo, "AresHintFusedBatch") and hasattr(self._algo, "AresScanAtFilterStats")
+
+    def hint_fused_batch(self, query, batch_rows, prev_size, measure_bytes, stream=None, device=0):
+        """AresHintFusedBatch: what the stream's next InitIndexVector ... HashReduce sequence will be (no result)."""
+        fn = self._algo.AresHintFusedBatch  # AttributeError: this library has no such entry point
+        fn.argtypes, fn.restype = [C.POINTER(FusedQuery), C.c_int, C.c_int, C.c_int, _S, _I], None
+        fn(C.byref(query), int(batch_rows), int(prev_size), int(measure_bytes), stream, device)
+
+    SCAN_AT_FILTER_COUNTERS = ("hints", "scans", "honoured", "declined", "discard_plan", "discard_shape", "discard_touched",
+                               "discard_abandoned", "retried", "latched")
+
+    def scan_at_filter_stats(self):
+        """AresScanAtFilterStats: {name: count} since the process started, in SCAN_AT_FILTER_COUNTERS' order."""
+        c = (C.c_ulonglong * len(self.SCAN_AT_FILTER_COUNTERS))()
+        self._algo.AresScanAtFilterStats.argtypes, self._algo.AresScanAtFilterStats.restype = [C.POINTER(C.c_ulonglong)], None
+        self._algo.AresScanAtFilterStats(c)
+        return {k: int(v) for k, v in zip(self.SCAN_AT_FILTER_COUNTERS, c)}
 
     @property
     def has_fused_select(self):

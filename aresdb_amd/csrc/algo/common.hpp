@@ -85,6 +85,7 @@ bool deferral_hooks_active();
 // something writes (or frees) [ptr, ptr + bytes): partition-grouped results that overlap are no longer
 // trusted (hash_reduce_lds.hip)
 void grouped_note_write(int device, const void *ptr, size_t bytes);
+void grouped_note_gone(int device, const void *ptr, size_t bytes);  // ... freed: what is known about the bytes dies with them
 void grouped_note_write(int device, const DimensionVector &v);  // the whole vector
 // [ptr, ptr + bytes) is about to be read: measure rows that an image-mode HashReduce left unwritten (they are defined by
 // the query's table image) are written first (hash_reduce_lds.hip)

@@ -410,6 +410,14 @@ MergeResult read_result_pinned(hipStream_t stream) {
 }  // namespace
 
 void grouped_note_write(int device, const void *ptr, size_t bytes) {
+  scan_ahead_note_touch(device, ptr, bytes, /*freed=*/false);  // (a hinted column is written: the hint and a scan launched from it die)
+  grouped_note_gone(device, ptr, bytes);
+}
+// ... or freed.  (A scan that was launched ahead of its HashReduce has run by then — its filter call waited for it — and what
+// it read is what a HashReduce that still finds the stream's queue will read: libmem.so keeps a block that pending work
+// reads aside, contents intact, or the queue is launched by the free and nothing is fused.  Only a hint nothing was launched
+// from yet dies: no speculative read of a freed block.)
+void grouped_note_gone(int device, const void *ptr, size_t bytes) {
   sorted_state_note_write(device, ptr, bytes);  // (sort_reduce_fused.hip: the row hashes kept beside a Sort + Reduce result)
   const uint8_t *lo = static_cast<const uint8_t *>(ptr);
   const uint8_t *hi = lo + (bytes ? bytes : 1);
@@ -627,9 +635,284 @@ static void fused_note_first_batch(size_t shape, int groups) {
   g_firstBatchGroups[shape] = groups;
 }
 
+// ---- which scan ("decide and prepare": shared by HashReduce and by a filter call that launches the scan ahead of it) ------
+// Everything here follows from the plan, the batch's rows and the size of the previous result: nothing is read from the
+// result vectors, so a caller that has only been TOLD what the batch will be (AresHintFusedBatch) decides as HashReduce will.
+static hr::Widen widen_of(const FusedPlanD &plan) {
+  hr::Widen widen;
+  widen.mode = plan.measureWidth == 8 ? 1 : 0;
+  widen.rk = plan.measure.f.rk;
+  widen.dtype = plan.measureDtype;
+  return widen;
+}
+static int fused_part_bits(int64_t length, bool narrow) { return std::max(part_bits_for(length), narrow ? 2 : 0); }  // (the generated merge needs >= 4 partitions)
+struct ScanChoice {
+  size_t shape = 0;  // of a first batch: what its cardinality is remembered under
+  int chunkTiles = 0;
+  bool compact = false, wantLean = false, wantTable = false;
+  RtcKernel lean, table;
+};
+// a: the call's aggregate (the TABLE scan is generated for it); null: only a DIRECT scan is of interest, none other is looked up
+static ScanChoice choose_scan(int device, const FusedPlanD &plan, int nd, int batchRows, int prevSize, int partBits, bool narrow, const AggSpec *a) {
+  ScanChoice c;
+  int expected = prevSize;
+  bool known = prevSize > 0;
+  const bool rtc = batchRows > 0 && rtc_scan_available();
+  if (rtc && prevSize == 0) {
+    const RtcSpec spec = rtc_spec_scan(plan, nd, 0, false);  // (only equality of shapes matters: the hash of its bytes)
+    c.shape = std::hash<std::string>()(std::string(reinterpret_cast<const char *>(&spec), sizeof(spec)));
+    std::lock_guard<std::mutex> lock(g_shapeMutex);
+    auto it = g_firstBatchGroups.find(c.shape);
+    if (it != g_firstBatchGroups.end()) {
+      expected = it->second;
+      known = true;
+    }
+  }
+  c.chunkTiles = compact_enabled() ? rtc_compact_chunk_tiles(batchRows, partBits) : 0;
+  c.compact = c.chunkTiles > 0;
+  // (ARES_LEAN_MIN_GROUPS=0 — tests — sends every batch, known shape or not, to the DIRECT kernels)
+  c.wantLean = rtc && expected >= lean_min_groups() && (known || lean_min_groups() <= 0);
+  // (a narrow shape nobody has seen has no adaptive generic kernel to find its cardinality out with: the TABLE scan takes
+  // it — right for any number of groups, rows that find the table full travel alone — and the next first batch knows)
+  c.wantTable = rtc && !c.wantLean && (known || narrow);
+  if (c.wantLean) c.lean = rtc_lookup(device, rtc_spec_scan(plan, nd, partBits, c.compact));
+  else if (c.wantTable && a) c.table = rtc_lookup(device, rtc_spec_table_scan(plan, nd, partBits, *a, widen_of(plan)));
+  return c;
+}
+// The regions of a DIRECT scan and what its records need to know ("prepare"): region A sized for rowsA rows, region B for
+// the batch.
+static void prepare_direct_scan(Regions &r, const FusedPlanD &plan, int partBits, int64_t rowsA, int batchRows, int prevSize, int streams,
+                                int chunkTiles, hipStream_t stream) {
+  SlowScope slow("make_regions");
+  make_regions(r, partBits, rowsA, batchRows, streams, 4, stream, chunkTiles > 0 ? static_cast<int>(kCompactLineRecords) : 8);
+  r.ws.widen = widen_of(plan);
+  r.ws.chunkRows = static_cast<uint32_t>(chunkTiles) * 4096u;
+  r.ws.rowBase = static_cast<uint32_t>(prevSize);
+}
+
+// ---- scan at filter --------------------------------------------------------------------------------------------------
+// A host that says what a batch will be BEFORE the batch's filters (AresHintFusedBatch) lets the batch's last filter be
+// counted by the compact DIRECT scan itself: the scan evaluates every filter per row anyway, so it is launched where the
+// filter's counting kernel would have been, leaves one survivor count per workgroup in the caller's pinned slot and its
+// records in regions that wait here ("the stash") for the stream's HashReduce — which takes them for its own scan's if
+// it decides, from the queue it finds, exactly what was decided from the hint, and scans as ever otherwise.
+// One entry per (device, stream).  The mutex is a leaf: nothing is called with it held (buffers go after the unlock).
+struct ScanStash {
+  Regions r;
+  FusedPlanD plan;
+  int nd, batchRows, prevSize, partBits, chunkTiles, slack;
+  RtcKernel lean;
+};
+namespace {
+struct AheadEntry {
+  int device;
+  hipStream_t stream;
+  bool live = false;    // a hint is in place ...
+  int inits = 0;        // ... and has seen this many InitIndexVector calls of the stream (1: its batch is running)
+  ScanHint hint;
+  std::shared_ptr<ScanStash> stash;
+  // a hint whose scans are thrown away costs a scan per batch: after two in a row the stream's hints are ignored until
+  // one describes another shape
+  int discardsInARow = 0;
+  bool latched = false;
+  FusedPlanD latchedShape;
+};
+std::mutex g_aheadMutex;
+std::vector<AheadEntry> g_ahead;
+std::atomic<unsigned long long> g_aheadCounters[kScanAheadCounters];
+
+AheadEntry *ahead_find(int device, hipStream_t stream) {  // caller holds g_aheadMutex
+  for (AheadEntry &e : g_ahead)
+    if (e.device == device && e.stream == stream) return &e;
+  return nullptr;
+}
+FusedPlanD shape_of(FusedPlanD plan) {  // the plan without its columns' addresses: what stays the same from batch to batch
+  for (int c = 0; c < kFusedCols; c++) {
+    plan.cols[c].vals = nullptr;
+    plan.cols[c].nulls = nullptr;
+    plan.cols[c].bitOff = 0;
+  }
+  return plan;
+}
+// caller holds g_aheadMutex: the entry's scan was launched for nothing
+void ahead_discarded(AheadEntry &e, int reason) {
+  scan_ahead_count(reason);
+  if (reason == kScanAheadDiscardRetry) return;  // (the scan was used; the batch itself needed more room)
+  if (++e.discardsInARow >= 2 && !e.latched) {
+    e.latched = true;
+    e.latchedShape = shape_of(e.hint.plan);
+  }
+}
+bool ranges_hit(const ScanHint &h, const uint8_t *lo, const uint8_t *hi) {
+  for (int k = 0; k < h.numRanges; k++)
+    if (h.ranges[k].lo < hi && lo < h.ranges[k].hi) return true;
+  return false;
+}
+}  // namespace
+
+void scan_ahead_count(int which) { g_aheadCounters[which].fetch_add(1, std::memory_order_relaxed); }
+void scan_ahead_stats(unsigned long long *out) {
+  for (int k = 0; k < kScanAheadCounters; k++) out[k] = g_aheadCounters[k].load(std::memory_order_relaxed);
+}
+bool scan_at_filter_enabled() {
+  static EnvSwitch<bool> on("ARES_SCAN_AT_FILTER", [](const char *e) { return !(e && e[0] == '0'); });
+  return on.get() && grouped_enabled();
+}
+
+void scan_hint_set(int device, hipStream_t stream, const ScanHint &hint) {
+  std::shared_ptr<ScanStash> old;
+  {
+    std::lock_guard<std::mutex> lock(g_aheadMutex);
+    AheadEntry *e = ahead_find(device, stream);
+    if (!e) {
+      g_ahead.emplace_back();
+      e = &g_ahead.back();
+      e->device = device;
+      e->stream = stream;
+    }
+    if (e->stash) ahead_discarded(*e, kScanAheadDiscardAbandoned);
+    old.swap(e->stash);
+    if (e->latched && fused_plan_equal(shape_of(hint.plan), e->latchedShape, hint.nd)) {
+      scan_ahead_count(kScanAheadLatched);
+      e->live = false;
+      return;
+    }
+    if (e->latched) {  // another shape: a new start
+      e->latched = false;
+      e->discardsInARow = 0;
+    }
+    e->hint = hint;
+    e->live = true;
+    e->inits = 0;
+    scan_ahead_count(kScanAheadHints);
+  }
+}
+
+void scan_hint_init_index(int device, hipStream_t stream) {
+  std::shared_ptr<ScanStash> old;
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  AheadEntry *e = ahead_find(device, stream);
+  if (!e) return;
+  if (e->stash) ahead_discarded(*e, kScanAheadDiscardAbandoned);  // its HashReduce never came
+  old.swap(e->stash);
+  if (e->live && ++e->inits > 1) e->live = false;
+}
+
+bool scan_hint_live(int device, hipStream_t stream, ScanHint *out) {
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  AheadEntry *e = ahead_find(device, stream);
+  if (!e || !e->live || e->inits != 1 || e->stash) return false;
+  *out = e->hint;
+  return true;
+}
+
+void scan_stash_put(int device, hipStream_t stream, std::shared_ptr<ScanStash> stash) {
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  AheadEntry *e = ahead_find(device, stream);
+  if (!e || !e->live) return;  // (the hint died meanwhile — a column was written: the scan's records go unread)
+  e->stash.swap(stash);
+  scan_ahead_count(kScanAheadScans);
+}
+
+std::shared_ptr<ScanStash> scan_stash_take(int device, hipStream_t stream) {
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  AheadEntry *e = ahead_find(device, stream);
+  if (!e || !e->stash) return nullptr;
+  std::shared_ptr<ScanStash> s;
+  s.swap(e->stash);
+  e->live = false;  // the hint described the sequence that ends here
+  return s;
+}
+
+void scan_stash_settled(int device, hipStream_t stream, int reason, bool blame) {
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  AheadEntry *e = ahead_find(device, stream);
+  if (reason == kScanAheadHonoured) {
+    scan_ahead_count(kScanAheadHonoured);
+    if (e) e->discardsInARow = 0;
+  } else if (e && blame) {
+    ahead_discarded(*e, reason);
+  } else {
+    scan_ahead_count(reason);
+  }
+}
+
+void scan_ahead_note_touch(int device, const void *ptr, size_t bytes, bool freed) {
+  const uint8_t *lo = static_cast<const uint8_t *>(ptr), *hi = lo + (bytes ? bytes : 1);
+  std::vector<std::shared_ptr<ScanStash>> dead;
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  for (AheadEntry &e : g_ahead) {
+    if (e.device != device || !(e.live || e.stash) || !ranges_hit(e.hint, lo, hi)) continue;
+    e.live = false;
+    if (e.stash && !freed) {
+      scan_ahead_count(kScanAheadDiscardTouched);  // (not the hint's fault: the latch does not count it)
+      dead.push_back(std::move(e.stash));
+      e.stash = nullptr;
+    }
+  }
+}
+
+void scan_ahead_stream_gone(int device, hipStream_t stream) {
+  std::shared_ptr<ScanStash> old;
+  std::lock_guard<std::mutex> lock(g_aheadMutex);
+  for (size_t i = 0; i < g_ahead.size(); i++)
+    if (g_ahead[i].device == device && g_ahead[i].stream == stream) {
+      if (g_ahead[i].stash) scan_ahead_count(kScanAheadDiscardAbandoned);
+      old.swap(g_ahead[i].stash);
+      g_ahead[i] = g_ahead.back();
+      g_ahead.pop_back();
+      return;
+    }
+}
+
+// "Decide and prepare" + "launch" from a hint: null unless the batch would take the compact DIRECT scan and that kernel is
+// loaded; otherwise the scan is on `stream`, its workgroups' survivor counts go to hostCount[0 .. *grid).
+std::shared_ptr<ScanStash> fused_scan_ahead(int device, const ScanHint &hint, hipStream_t stream, uint32_t *hostCount, int *grid) {
+  const FusedPlanD &plan = hint.plan;
+  const bool narrow = fused_plan_narrow(plan, hint.nd);
+  const int64_t length = static_cast<int64_t>(hint.batchRows) + hint.prevSize;
+  if (narrow || hint.batchRows <= 0 || length > INT32_MAX) return nullptr;
+  const int partBits = fused_part_bits(length, narrow);
+  const ScanChoice choice = choose_scan(device, plan, hint.nd, hint.batchRows, hint.prevSize, partBits, narrow, nullptr);
+  if (!choice.wantLean || !choice.lean || !choice.compact) return nullptr;
+  auto stash = std::make_shared<ScanStash>();
+  stash->plan = plan;
+  stash->nd = hint.nd;
+  stash->batchRows = hint.batchRows;
+  stash->prevSize = hint.prevSize;
+  stash->partBits = partBits;
+  stash->chunkTiles = choice.chunkTiles;
+  stash->slack = record_stream_slack();
+  stash->lean = choice.lean;
+  const int streams = rtc_scan_grid(hint.batchRows);
+  static_assert(kMaxStreams <= kPinnedWords, "one survivor count per workgroup fits the pinned slot");
+  prepare_direct_scan(stash->r, plan, partBits, /*rowsA=*/0, hint.batchRows, hint.prevSize, streams, choice.chunkTiles, stream);
+  rtc_scan_launch(choice.lean, RTC_SCAN_COMPACT, plan, static_cast<uint32_t>(hint.prevSize), hint.batchRows, stash->r.ws, stream, hostCount);
+  *grid = streams;
+  return stash;
+}
+
 int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, const DimensionVector &prevKeys,
                           const uint8_t *prevValues, int prevSize, const DimensionVector &outKeys, uint8_t *outValues,
-                          const AggSpec &a, hipStream_t stream) {
+                          const AggSpec &a, hipStream_t stream, std::shared_ptr<ScanStash> stash) {
+  // What becomes of a stash is settled ONCE, where the call ends (or throws): "honoured" only when the call ends with a result
+  // merged from the stashed regions; a stash that was taken and whose round then ran again or fell back (stale ranges, a
+  // record stream overflow) counts as retried; one the call never got to look at — declined early: a kernel still being
+  // compiled, an empty call — is dropped without blame: that is not the hint's fault, and the latch does not count it.
+  struct Settle {
+    std::shared_ptr<ScanStash> &stash;
+    int device;
+    hipStream_t stream;
+    bool taken = false, merged = false;
+    void rescanned() {  // the round that took the stash did not end the call
+      if (taken) scan_stash_settled(device, stream, kScanAheadDiscardRetry);
+      taken = false;
+    }
+    ~Settle() {
+      if (stash) scan_stash_settled(device, stream, kScanAheadDiscardShape, /*blame=*/false);
+      else if (taken) scan_stash_settled(device, stream, merged ? kScanAheadHonoured : kScanAheadDiscardRetry);
+    }
+  } settle{stash, device, stream};
   SlotWidths slots;
   if (!slot_widths(outKeys.NumDimsPerDimWidth, &slots)) return kFusedUnavailable;
   const int nd = slots.nd;
@@ -641,7 +924,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   const int mw = plan.measureWidth;
   const int64_t length = static_cast<int64_t>(batchRows) + prevSize;
   if (length == 0) return 0;
-  const int partBits = std::max(part_bits_for(length), narrow ? 2 : 0);  // (the generated merge needs >= 4 partitions)
+  const int partBits = fused_part_bits(length, narrow);
   const int numParts = 1 << partBits;
   const size_t prevCapacity = static_cast<size_t>(prevKeys.VectorCapacity);
   const size_t outCapacity = static_cast<size_t>(outKeys.VectorCapacity);
@@ -669,36 +952,14 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   // call whose specialised kernel is not loaded yet (it is compiled in the background, never inside a query).
   // The first batch of a query has no previous groups to judge by: it goes by what the first batch of
   // the same plan shape (expressions and divisors, not columns or comparison constants) produced the last time.
-  hr::Widen widen;
-  widen.mode = mw == 8 ? 1 : 0;
-  widen.rk = plan.measure.f.rk;
-  widen.dtype = plan.measureDtype;
-  size_t shape = 0;
-  int expected = prevSize;
-  bool known = prevSize > 0;
-  const bool rtc = batchRows > 0 && rtc_scan_available();
-  if (rtc && prevSize == 0) {
-    const RtcSpec spec = rtc_spec_scan(plan, nd, 0, false);  // (only equality of shapes matters: the hash of its bytes)
-    shape = std::hash<std::string>()(std::string(reinterpret_cast<const char *>(&spec), sizeof(spec)));
-    std::lock_guard<std::mutex> lock(g_shapeMutex);
-    auto it = g_firstBatchGroups.find(shape);
-    if (it != g_firstBatchGroups.end()) {
-      expected = it->second;
-      known = true;
-    }
-  }
-  const int chunkTiles = compact_enabled() ? rtc_compact_chunk_tiles(batchRows, partBits) : 0;
-  const bool compact = chunkTiles > 0;
-  const RtcKind leanKind = compact ? RTC_SCAN_COMPACT : RTC_SCAN_LINES16;
-  RtcKernel lean, table, tableMerge, narrowMerge;
+  const hr::Widen widen = widen_of(plan);
   SlowScope slowWhole("fused_hash_reduce_run");
-  // (ARES_LEAN_MIN_GROUPS=0 — tests — sends every batch, known shape or not, to the DIRECT kernels)
-  const bool wantLean = rtc && expected >= lean_min_groups() && (known || lean_min_groups() <= 0);
-  // (a narrow shape nobody has seen has no adaptive generic kernel to find its cardinality out with: the TABLE scan takes
-  // it — right for any number of groups, rows that find the table full travel alone — and the next first batch knows)
-  const bool wantTable = rtc && !wantLean && (known || narrow);
-  if (wantLean) lean = rtc_lookup(device, rtc_spec_scan(plan, nd, partBits, compact));
-  else if (wantTable) table = rtc_lookup(device, rtc_spec_table_scan(plan, nd, partBits, a, widen));
+  const ScanChoice choice = choose_scan(device, plan, nd, batchRows, prevSize, partBits, narrow, &a);
+  const size_t shape = choice.shape;
+  const int chunkTiles = choice.chunkTiles;
+  const bool compact = choice.compact, wantLean = choice.wantLean, wantTable = choice.wantTable;
+  const RtcKind leanKind = compact ? RTC_SCAN_COMPACT : RTC_SCAN_LINES16;
+  RtcKernel lean = choice.lean, table = choice.table, tableMerge, narrowMerge;
   // ---- table image (see "table images" above): 2 = the merge starts from the image the previous call left with the input
   // vectors; 1 = the ordinary specialised merge, which leaves an image for the next call.  DIRECT-mode batches only.
   int imageMode = 0;
@@ -761,13 +1022,45 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
     launched = true;
     const int streams = batchRows > 0 ? (lean ? rtc_scan_grid(batchRows) : table ? 0 : grid_for(batchRows)) : 0;
     Regions r;
-    {
+    // DIRECT mode writes region A only with previous groups that are not grouped by partition yet; sizing it for
+    // the batch as well made the first DIRECT batch of a process allocate (and the driver clear) 2.7 GB more
+    const int64_t rowsA = !lean ? length : (prevSize > 0 && !grouped && imageMode != 2) ? prevSize : 0;
+    // The batch's scan may have run already, launched by the batch's last filter from a hint (scan at filter): its regions
+    // are this call's if everything that shaped them is what this call has just decided.  Once: a second round scans again.
+    bool scanned = false;
+    if (stash) {
+      const std::shared_ptr<ScanStash> st = std::move(stash);
+      stash = nullptr;
+      int why = -1;
+      if (!lean || !compact || st->nd != nd || !fused_plan_equal(st->plan, plan, nd)) why = kScanAheadDiscardPlan;
+      else if (st->batchRows != batchRows || st->prevSize != prevSize || st->partBits != partBits || st->chunkTiles != chunkTiles ||
+               st->slack != record_stream_slack() || st->lean != lean || st->r.ws.streams != streams || rowsA != 0)
+        why = kScanAheadDiscardShape;
+      if (hr_trace_enabled())  // diagnostics
+        fprintf(stderr, "fused_hash_reduce_run: scan at filter %s | lean %d compact %d nd %d/%d plan equal %d | rows %d/%d prev %d/%d partBits %d/%d "
+                        "chunkTiles %d/%d slack %d/%d kernel %d streams %d/%d rowsA %lld\n",
+                why < 0 ? "honoured" : why == kScanAheadDiscardPlan ? "discarded (plan)" : "discarded (shape)", lean ? 1 : 0, compact ? 1 : 0, st->nd, nd,
+                fused_plan_equal(st->plan, plan, nd) ? 1 : 0, st->batchRows, batchRows, st->prevSize, prevSize, st->partBits, partBits, st->chunkTiles,
+                chunkTiles, st->slack, record_stream_slack(), st->lean == lean ? 1 : 0, st->r.ws.streams, streams, static_cast<long long>(rowsA));
+      if (why < 0) {
+        r = std::move(st->r);
+        scanned = true;
+        settle.taken = true;
+      }
+      // (a previous result that is not grouped — it has just moved to larger buffers — is the host's transient state, not a
+      // wrong hint: the two-discard latch does not count it)
+      const bool onlyRegionA = why == kScanAheadDiscardShape && st->batchRows == batchRows && st->prevSize == prevSize && st->partBits == partBits &&
+                               st->chunkTiles == chunkTiles && st->slack == record_stream_slack() && st->lean == lean && st->r.ws.streams == streams;
+      if (why >= 0) scan_stash_settled(device, stream, why, !onlyRegionA);
+    } else {
+      settle.rescanned();
+    }
+    if (scanned) {
+    } else if (lean) {
+      prepare_direct_scan(r, plan, partBits, rowsA, batchRows, prevSize, streams, chunkTiles, stream);
+    } else {
       SlowScope slow("make_regions");
-      // DIRECT mode writes region A only with previous groups that are not grouped by partition yet; sizing it for
-      // the batch as well made the first DIRECT batch of a process allocate (and the driver clear) 2.7 GB more
-      const int64_t rowsA = !lean ? length : (prevSize > 0 && !grouped && imageMode != 2) ? prevSize : 0;
-      make_regions(r, partBits, rowsA, batchRows, streams, lean ? 4 : 3, stream,
-                   !lean ? 0 : compact ? static_cast<int>(kCompactLineRecords) : 8);
+      make_regions(r, partBits, rowsA, batchRows, streams, 3, stream, 0);
     }
     Workspace &ws = r.ws;
     ws.widen = widen;
@@ -808,7 +1101,8 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
         ARES_LAUNCH("hr_partition4_kernel", (hr_partition4_kernel<ND, 4>), grid_for(prevSize), kThreads, stream,        \
                     prevKeys.DimValues, prevCapacity, prevValues, 0u, a, prevSize, wsPrev, 0);                         \
     }                                                                                                                  \
-    if (batchRows > 0 && lean)                                                                                         \
+    if (scanned) {                                                                                                     \
+    } else if (batchRows > 0 && lean)                                                                                  \
       rtc_scan_launch(lean, leanKind, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);                   \
     else if (batchRows > 0 && table)                                                                                   \
       rtc_scan_launch(table, RTC_SCAN_TABLE, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);            \
@@ -831,7 +1125,8 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
     switch (nd) {
       ARES_FUSED_CASE(1) ARES_FUSED_CASE(2) ARES_FUSED_CASE(3) ARES_FUSED_CASE(4)
       default:  // five to eight dimensions: the generated kernels only (the plan counts as narrow: both were looked up above)
-        if (batchRows > 0 && lean) rtc_scan_launch(lean, leanKind, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
+        if (scanned) {
+        } else if (batchRows > 0 && lean) rtc_scan_launch(lean, leanKind, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
         else if (batchRows > 0 && table) rtc_scan_launch(table, RTC_SCAN_TABLE, plan, static_cast<uint32_t>(prevSize), batchRows, ws, stream);
         rtc_merge_launch(leanMerge ? leanMerge : tableMerge, plan, prevKeys.DimValues, prevCapacity, prevValues, static_cast<uint32_t>(prevSize),
                          outKeys.DimValues, outCapacity, outValues, ws, stream, imagePtr, result_slot());
@@ -888,6 +1183,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
   if (res.overflow) {
     return -1;
   }
+  settle.merged = true;
   fused_note_first_batch(shape, static_cast<int>(res.groups));
   if (shape && !lean && !table) {
     // the next first batch of this shape takes the specialised kernels: have them built now (in the background)

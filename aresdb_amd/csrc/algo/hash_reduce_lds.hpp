@@ -3,6 +3,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "aggregate.hpp"
 #include "ares_algorithm.h"
 #include "dim_layout.hpp"
@@ -69,6 +71,28 @@ struct FusedPlanD {
   // "null measure": the pair {0, 0} instead of {average, 1}
   int measureAvg;
 };
+// Two plans describe the same scan over the same columns: every field a scan, a merge or a spec maker reads, one by one
+// (the structs hold padding: their bytes are not compared).  What a hinted plan and the plan HashReduce derives from the
+// stream's queue must satisfy before a scan launched from the first is taken for the second's.
+inline bool fused_expr_equal(const FusedExpr &a, const FusedExpr &b) {
+  return a.col == b.col && a.outKind == b.outKind && a.f.akind == b.f.akind && a.f.arity == b.f.arity && a.f.functor == b.f.functor &&
+         a.f.I == b.f.I && a.f.rk == b.f.rk && a.f.bkind == b.f.bkind && a.f.bbits == b.f.bbits && a.f.bok == b.f.bok &&
+         a.f.divLike == b.f.divLike && (a.f.step ? a.f.step : 4) == (b.f.step ? b.f.step : 4);
+}
+inline bool fused_plan_equal(const FusedPlanD &a, const FusedPlanD &b, int nd) {
+  if (a.numCols != b.numCols || a.numFilters != b.numFilters || a.measureDtype != b.measureDtype || a.measureWidth != b.measureWidth ||
+      a.identity != b.identity || a.measureAvg != b.measureAvg)
+    return false;
+  for (int c = 0; c < a.numCols; c++)
+    if (a.cols[c].vals != b.cols[c].vals || a.cols[c].nulls != b.cols[c].nulls || a.cols[c].bitOff != b.cols[c].bitOff ||
+        (a.cols[c].step ? a.cols[c].step : 4) != (b.cols[c].step ? b.cols[c].step : 4))
+      return false;
+  for (int k = 0; k < a.numFilters; k++)
+    if (!fused_expr_equal(a.filters[k], b.filters[k])) return false;
+  for (int d = 0; d < nd; d++)
+    if (!fused_expr_equal(a.dims[d], b.dims[d]) || (a.dimWidth[d] ? a.dimWidth[d] : 4) != (b.dimWidth[d] ? b.dimWidth[d] : 4)) return false;
+  return fused_expr_equal(a.measure, b.measure);
+}
 inline int fused_dim_width(const FusedPlanD &p, int d) { return p.dimWidth[d] ? p.dimWidth[d] : 4; }
 inline int fused_col_step(const FusedPlanD &p, int c) { return p.cols[c].step ? static_cast<int>(p.cols[c].step) : 4; }
 inline bool fused_plan_narrow(const FusedPlanD &p, int nd) {
@@ -181,8 +205,52 @@ constexpr int kFusedUnavailable = -2;
 // the slack — it stays grown for the process — and runs again instead of leaving the fast path.
 int record_stream_slack();
 bool grow_record_stream_slack();  // false: already at its limit (8 x the mean)
+// stash: the batch's scan as a filter call launched it ahead of this call (below), or null.  It is taken for this call's own
+// scan when the call decides exactly what was decided then — same plan, rows, previous size, partitions, record format and
+// stream room, no region A — and dropped otherwise: the call then scans as ever.
+struct ScanStash;
 int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, const DimensionVector &prevKeys,
                           const uint8_t *prevValues, int prevSize, const DimensionVector &outKeys, uint8_t *outValues,
-                          const AggSpec &a, hipStream_t stream);
+                          const AggSpec &a, hipStream_t stream, std::shared_ptr<ScanStash> stash = nullptr);
+
+// ---- scan at filter (hash_reduce_lds.hip; the filter call itself: transform.hip) ----------------------------------------
+// What AresHintFusedBatch said about a stream's next InitIndexVector ... HashReduce sequence.
+struct ScanHint {
+  FusedPlanD plan;  // built like plan_from_queue builds HashReduce's: fused_plan_dim x nd, fused_plan_measure, fused_plan_filters
+  int nd, batchRows, prevSize;
+  FastOperands filters[kFusedFilters];  // the plan's filters with their columns: what the journal must hold when the last one is called
+  struct Range {
+    const uint8_t *lo, *hi;
+  } ranges[2 * kFusedCols];  // bytes the scan reads: a write or a free inside ends the hint and whatever was launched from it
+  int numRanges;
+};
+// AresScanAtFilterStats: one counter each, in this order
+enum ScanAheadCounter {
+  kScanAheadHints,             // hints taken
+  kScanAheadScans,             // scans launched at a filter
+  kScanAheadHonoured,          // ... whose regions HashReduce merged its result from (counted when that call ends well)
+  kScanAheadDeclined,          // hints declined (short column, shape, a switch)
+  kScanAheadDiscardPlan,       // scans discarded: HashReduce derived another plan
+  kScanAheadDiscardShape,      // ... other rows, previous size, partitions, kernel or stream room, or region A was needed
+  kScanAheadDiscardTouched,    // ... a hinted column was written or freed
+  kScanAheadDiscardAbandoned,  // ... the stream's HashReduce never came (or did not consume the stream's queue)
+  kScanAheadDiscardRetry,      // scans taken whose call then scanned again or fell back (stale ranges, record stream overflow)
+  kScanAheadLatched,           // hints ignored: the stream's last two scans were discarded
+  kScanAheadCounters
+};
+void scan_ahead_count(int which);
+void scan_ahead_stats(unsigned long long *out);
+bool scan_at_filter_enabled();  // ARES_SCAN_AT_FILTER (on unless 0), and the sibling libmem.so reports writes and frees
+void scan_hint_set(int device, hipStream_t stream, const ScanHint &hint);
+void scan_hint_init_index(int device, hipStream_t stream);  // InitIndexVector on the stream: the hint's batch begins, or has ended
+bool scan_hint_live(int device, hipStream_t stream, ScanHint *out);  // the hint of the batch that is running, nothing launched from it yet
+std::shared_ptr<ScanStash> fused_scan_ahead(int device, const ScanHint &hint, hipStream_t stream, uint32_t *hostCount, int *grid);
+void scan_stash_put(int device, hipStream_t stream, std::shared_ptr<ScanStash> stash);
+std::shared_ptr<ScanStash> scan_stash_take(int device, hipStream_t stream);
+// reason: kScanAheadHonoured or a discard counter; blame: the discard counts towards the stream's two-discard latch
+void scan_stash_settled(int device, hipStream_t stream, int reason, bool blame = true);
+// a byte range is written (or a copy touches it), or freed: hints that read it die; scans launched from them die unless `freed`
+void scan_ahead_note_touch(int device, const void *ptr, size_t bytes, bool freed);
+void scan_ahead_stream_gone(int device, hipStream_t stream);
 
 }  // namespace ares

@@ -80,6 +80,7 @@ struct RtcArgs {  // mirrors `struct Args` of the generated source (args_text, h
   uint32_t *countsB;
   uint32_t *overflow;
   uint64_t *phases;
+  uint32_t *hostCount;  // compact scan: one survivor count per workgroup, in host memory the device can write (null: none)
   uint4 *recA;
   uint32_t *cursorsA;
   uint64_t capA;
@@ -548,7 +549,7 @@ void launch(const RtcKernel &kernel, void *args, size_t size, unsigned grid, hip
 
 // `plan`: the columns and constants of a scan (RtcArgs::k: comparison constants converted to the common kind by the host)
 void launch_scan(const RtcKernel &kernel, const FusedPlanD &plan, uint32_t rowBase, int length, const hr::Workspace &ws, int grid,
-                 uint32_t chunkTiles, uint32_t pad, hipStream_t stream, const char *name) {
+                 uint32_t chunkTiles, uint32_t pad, hipStream_t stream, const char *name, uint32_t *hostCount = nullptr) {
   RtcArgs args;
   fill_columns(args, plan);
   for (int k = 0; k < plan.numFilters && k < kFusedFilters; k++)
@@ -557,6 +558,7 @@ void launch_scan(const RtcKernel &kernel, const FusedPlanD &plan, uint32_t rowBa
   args.recB = ws.recB;
   args.countsB = ws.countsB;
   args.overflow = ws.outCount + 1;
+  args.hostCount = hostCount;
   args.recA = ws.recA;
   args.cursorsA = ws.cursorsA;
   args.capA = ws.capA;
@@ -625,12 +627,12 @@ RtcKernel rtc_lookup(int device, const RtcSpec &spec, bool wait) {
 }
 
 void rtc_scan_launch(const RtcKernel &kernel, RtcKind kind, const FusedPlanD &plan, uint32_t rowBase, int length, const hr::Workspace &ws,
-                     hipStream_t stream) {
+                     hipStream_t stream, uint32_t *hostCount) {
   // (TABLE: one workgroup per tile up to a full device — its records do not grow with it)
   const int grid = kind == RTC_SCAN_TABLE ? rtc_scan_grid(length) : ws.streams;
   const uint32_t chunkTiles = kind == RTC_SCAN_COMPACT ? ws.chunkRows / 4096u : 0u;
   launch_scan(kernel, plan, rowBase, length, ws, grid, chunkTiles, 0u, stream,
-              kind == RTC_SCAN_TABLE ? "hr_table_scan_rtc" : rtc_entry_name(kind));
+              kind == RTC_SCAN_TABLE ? "hr_table_scan_rtc" : rtc_entry_name(kind), kind == RTC_SCAN_COMPACT ? hostCount : nullptr);
 }
 
 void rtc_vector_scan_launch(const RtcKernel &kernel, RtcKind kind, const uint8_t *dimValues, size_t capacity, const void *measures, int nd,

@@ -30,9 +30,10 @@ int rtc_compact_chunk_tiles(int64_t rows, int partBits);
 RtcKernel rtc_lookup(int device, const RtcSpec &spec, bool wait = false);
 
 // A plan-sourced scan (`kind`: what the kernel was looked up as) over rows [0, length) of the plan's columns; records
-// number their rows from rowBase.
+// number their rows from rowBase.  hostCount (RTC_SCAN_COMPACT only): ws.streams words of host memory the device can write
+// (the calling thread's pinned slot): every workgroup leaves the number of its rows that passed the filters there.
 void rtc_scan_launch(const RtcKernel &kernel, RtcKind kind, const FusedPlanD &plan, uint32_t rowBase, int length, const hr::Workspace &ws,
-                     hipStream_t stream);
+                     hipStream_t stream, uint32_t *hostCount = nullptr);
 // A vector-sourced scan (RTC_VECTOR_SCAN, RTC_SORT_VECTOR_SCAN, RTC_HLL_SCAN) over rows [rowBase, rowBase + length) of a
 // materialised dimension vector (widths: as the spec's, null = all four bytes) and the `length` measures at `measures`.
 // totalPartBits / spread: Sort + Reduce's level-1 partition (rtc_spec_sort_vector_scan).

@@ -131,7 +131,7 @@ bool plain_store(int rk, int outKind) { return rk == outKind || (rk != K_F32 && 
 
 std::string args_text() {
   std::ostringstream o;
-  o << "struct Args { const u32 *vals[" << kFusedCols << "]; const u8 *nulls[" << kFusedCols << "]; u32 *recB; u32 *countsB; u32 *overflow; u64 *phases;\n"
+  o << "struct Args { const u32 *vals[" << kFusedCols << "]; const u8 *nulls[" << kFusedCols << "]; u32 *recB; u32 *countsB; u32 *overflow; u64 *phases; u32 *hostCount;\n"
        "              uint4 *recA; u32 *cursorsA; u64 capA; u32 bitOff[" << kFusedCols << "]; u32 rowBase; int length; u32 capB; u32 chunkTiles;\n"
        "              u32 k[" << kNumConsts << "]; u32 pad; };\n";
   return o.str();
@@ -377,7 +377,7 @@ static void kernel_body_compact(std::ostringstream &o, const RtcSpec &s) {
        "  __shared__ u32 sTotalLines;\n"
        "  const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;\n"
        "  for (u32 p = tid; p < NP; p += 1024u) { sCount[0][p] = 0u; sCount[1][p] = 0u; }\n"
-       "  u32 myLeftN = 0u, myCursor = 0u;\n"    // thread p < NP keeps partition p's leftover count and stream cursor in registers
+       "  u32 myLeftN = 0u, myCursor = 0u, mySeen = 0u;\n"    // thread p < NP keeps partition p's leftover count, stream cursor and survivors in registers
        "  __syncthreads();\n"
        "  u64 *myB = reinterpret_cast<u64 *>(a.recB) + (u64)blockIdx.x * NP * a.capB * 16u;\n"  // capB: lines per stream
        "  const u32 numTiles = ((u32)a.length + T - 1u) / T;\n"
@@ -409,6 +409,7 @@ static void kernel_body_compact(std::ostringstream &o, const RtcSpec &s) {
        "    u32 myCount = 0u, myLeft = 0u;\n"
        "    if (tid < NP) { myCount = cnt[tid]; myLeft = myLeftN; }\n"
        "    const u32 myHave = myCount + myLeft, myLines = myHave / LR;\n"
+       "    mySeen += myCount;\n"               // alive[] summed per partition: exact whatever the record streams hold
        "    const u32 packed = (myCount << 16) | myLines;\n"
        "    const u32 incl = wave_incl_scan(packed);\n"
        "    if (lane == 63u) sWave[wave] = incl;\n"
@@ -499,6 +500,13 @@ static void kernel_body_compact(std::ostringstream &o, const RtcSpec &s) {
        "    if (left && fits) STORE_LINE(&myB[((u64)p * a.capB + cur) * 16u + q], r8 ? rec : hdr);\n"
        "    if (left && !fits) *a.overflow = 1u;\n"
        "    if (q == 0u) a.countsB[(u64)blockIdx.x * NP + p] = cur * LR + ((left && fits) ? left : 0u);\n"
+       "  }\n"
+       // the rows that passed the filters, one word per workgroup, for a host that owes a filter's count (null: nobody asked)
+       "  if (a.hostCount) {\n"
+       "    const u32 seen = wave_incl_scan(mySeen);\n"
+       "    if (lane == 63u) sWave[wave] = seen;\n"
+       "    __syncthreads();\n"
+       "    if (tid == 0u) { u32 t = 0u; for (u32 w = 0u; w < 16u; w++) t += sWave[w]; a.hostCount[blockIdx.x] = t; }\n"
        "  }\n"
        "  PH(6)\n"
        "  PH_OUT\n"

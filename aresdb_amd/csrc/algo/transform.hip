@@ -262,6 +262,10 @@ struct PendingCompact {
   std::vector<LazyFilter> todo;
   int n0 = 0, applied = 0, lastCount = 0;
   std::shared_ptr<StreamBuffer> bits;
+  // The last of `todo` was counted by the batch's fused scan (scan at filter): counted, but NO survivor bits exist.  A null
+  // `bits` otherwise means "no filter yet, every row alive", so a further filter must not be counted in row space over this
+  // entry: it takes the replay (run_compaction, which re-evaluates from the operands) and the two-phase filter.
+  bool noBits = false;
   PredictedFilter predicted;
   uint64_t generation = 0;  // of the filter that was booked last (DeferState::filterGeneration)
 };
@@ -1466,8 +1470,26 @@ bool row_space_eligible(int device, hipStream_t stream, const uint32_t *indexVec
     return false;
   auto c = t_state->compactions.find(indexVector);
   if (j->second.filters.empty()) return n == j->second.n0 && c == t_state->compactions.end();
-  return c != t_state->compactions.end() && !c->second.todo.empty() && c->second.stream == stream &&
+  return c != t_state->compactions.end() && !c->second.todo.empty() && c->second.stream == stream && !c->second.noBits &&
          c->second.applied + c->second.todo.size() == j->second.filters.size() && c->second.lastCount == n;
+}
+
+// caller holds the device's DeferLock.  The batch's first row-space filter: the vector is iota(0 .. n), nothing applied
+std::map<const uint32_t *, PendingCompact>::iterator open_row_space(hipStream_t stream, uint32_t *indexVector, bool virtualIdx, int n) {
+  PendingCompact fresh{};
+  fresh.stream = stream;
+  fresh.idx = indexVector;
+  fresh.virtualIdx = virtualIdx;
+  fresh.n0 = n;
+  fresh.applied = 0;
+  fresh.lastCount = n;
+  return t_state->compactions.emplace(indexVector, fresh).first;
+}
+// ... and every row-space filter's shape goes into the stream's history of the running batch (what predictions go by)
+FilterShape note_filter_shape(FilterHistory &h, const PendingCompact &c, const FastOperands &f) {
+  const FilterShape shape{f.akind, f.functor, f.I, f.bkind, f.bbits, f.bok, !c.todo.empty() && same_column(c.todo.back().f, f)};
+  h.current.push_back(shape);
+  return shape;
 }
 
 // The call itself.  f: the filter (idx and pad are ignored: rows = positions).  Returns the survivor count.
@@ -1495,25 +1517,15 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
       auto jr = t_state->journals.find(indexVector);
       const size_t journalled = (jr != t_state->journals.end() && jr->second.valid) ? jr->second.filters.size() : 0;
       const bool first = ins == t_state->compactions.end() && journalled == 1 && jr->second.n0 == n;
-      const bool next = ins != t_state->compactions.end() && !ins->second.todo.empty() && ins->second.stream == stream &&
+      const bool next = ins != t_state->compactions.end() && !ins->second.todo.empty() && ins->second.stream == stream && !ins->second.noBits &&
                         ins->second.applied + ins->second.todo.size() + 1 == journalled && ins->second.lastCount == n;
       if (!first && !next) return -1;
     }
-    if (ins == t_state->compactions.end()) {  // the batch's first filter: the vector is iota(0 .. n)
-      PendingCompact fresh{};
-      fresh.stream = stream;
-      fresh.idx = indexVector;
-      fresh.virtualIdx = virtualIdx;
-      fresh.n0 = n;
-      fresh.applied = 0;
-      fresh.lastCount = n;
-      ins = t_state->compactions.emplace(indexVector, fresh).first;
-    }
+    if (ins == t_state->compactions.end()) ins = open_row_space(stream, indexVector, virtualIdx, n);
     PendingCompact &c = ins->second;
     FilterHistory &h = t_state->filterHistory[stream];
-    FilterShape shape{f.akind, f.functor, f.I, f.bkind, f.bbits, f.bok, !c.todo.empty() && same_column(c.todo.back().f, f)};
-    const size_t k = h.current.size();
-    h.current.push_back(shape);
+    const FilterShape shape = note_filter_shape(h, c, f);
+    const size_t k = h.current.size() - 1;
     if (c.predicted.valid && same_filter(c.predicted.g, f)) {  // counted together with the previous filter: no kernel
       const int count = c.predicted.count;
       c.todo.push_back(LazyFilter{f, colRows, pred, n, keep});
@@ -1587,6 +1599,66 @@ int run_filter_rows(int device, hipStream_t stream, FastOperands f, uint32_t *in
         it->second.predicted.bits = bits2;
       }
     }
+    auto j = t_state->journals.find(indexVector);
+    if (j != t_state->journals.end() && j->second.valid) j->second.lastCount = static_cast<int>(count);
+  }
+  return static_cast<int>(count);
+}
+
+// Scan at filter.  The call is the LAST filter of the batch the stream's hint describes (AresHintFusedBatch) and the journal
+// holds exactly the hinted filters: the batch's compact DIRECT scan — which evaluates every filter per row anyway — is
+// launched in filter_rows_kernel's place, counts the survivors per workgroup into the calling thread's pinned slot and
+// leaves its records stashed for the stream's HashReduce.  Decision, launch, booking and stash happen under ONE lock
+// acquisition (I5).  The filter is booked exactly like a counted one, except that no survivor bits exist afterwards
+// (PendingCompact::noBits).  -1: not such a call (the journal already holds the filter; the caller counts it as ever).
+// A record stream that overflows does not touch the count: the scan goes on evaluating with its cursor clamped.
+int run_filter_scan(int device, hipStream_t stream, FastOperands f, uint32_t *indexVector, uint8_t *pred, int n, uint32_t colRows,
+                    bool virtualIdx, const std::shared_ptr<StreamBuffer> &keep) {
+  ScanHint hint;
+  if (keep || !scan_at_filter_enabled() || !scan_hint_live(device, stream, &hint)) return -1;
+  f.idx = nullptr;
+  f.pad = 0;
+  int grid = 0;
+  uint64_t generation = 0;
+  {
+    DeferLock lock(device);
+    auto jr = t_state->journals.find(indexVector);
+    if (jr == t_state->journals.end() || !jr->second.valid || jr->second.stream != stream || jr->second.start != 0 ||
+        jr->second.n0 != hint.batchRows || jr->second.filters.size() != static_cast<size_t>(hint.plan.numFilters))
+      return -1;
+    const FilterJournal &j = jr->second;
+    for (size_t k = 0; k < j.filters.size(); k++)
+      if (!same_filter(j.filters[k], hint.filters[k]) || j.colRows[k] < static_cast<uint32_t>(j.n0)) return -1;
+    auto ins = t_state->compactions.find(indexVector);
+    const size_t journalled = j.filters.size();
+    const bool first = ins == t_state->compactions.end() && journalled == 1 && j.n0 == n;
+    const bool next = ins != t_state->compactions.end() && !ins->second.todo.empty() && ins->second.stream == stream && !ins->second.noBits &&
+                      ins->second.applied + ins->second.todo.size() + 1 == journalled && ins->second.lastCount == n;
+    if (!first && !next) return -1;
+    if (next && ins->second.predicted.valid && same_filter(ins->second.predicted.g, f)) return -1;  // (counted with the previous filter: no kernel at all)
+    std::shared_ptr<ScanStash> stash = fused_scan_ahead(device, hint, stream, reinterpret_cast<uint32_t *>(pinned_words()), &grid);
+    if (!stash) return -1;  // (not a batch for the compact DIRECT scan, or its kernel is not loaded yet)
+    if (ins == t_state->compactions.end()) ins = open_row_space(stream, indexVector, virtualIdx, n);
+    PendingCompact &c = ins->second;
+    note_filter_shape(t_state->filterHistory[stream], c, f);
+    c.predicted = PredictedFilter{};
+    // booked before the count is known, like a counted filter: a flush from another thread applies it with the others
+    c.todo.push_back(LazyFilter{f, colRows, pred, n, keep});
+    c.bits = nullptr;
+    c.noBits = true;
+    c.lastCount = -1;
+    generation = ++t_state->filterGeneration;
+    c.generation = generation;
+    scan_stash_put(device, stream, std::move(stash));
+  }
+  hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+  const volatile uint32_t *parts = reinterpret_cast<const volatile uint32_t *>(pinned_words());
+  uint32_t count = 0;
+  for (int b = 0; b < grid; b++) count += parts[b];
+  {
+    DeferLock lock(device);
+    auto it = t_state->compactions.find(indexVector);
+    if (it != t_state->compactions.end() && it->second.generation == generation) it->second.lastCount = static_cast<int>(count);
     auto j = t_state->journals.find(indexVector);
     if (j != t_state->journals.end() && j->second.valid) j->second.lastCount = static_cast<int>(count);
   }
@@ -1746,6 +1818,8 @@ static int run_filter(const InputVector *ins, int arity, uint32_t *indexVector, 
   else
     journal_filter(device, indexVector, nullptr, 0, 0);
   if (rowSpace && fast && journal_is_valid(device, indexVector)) {
+    const int scanned = run_filter_scan(device, stream, f, indexVector, pred, n, p.a.length, virtualIdx, decoded);
+    if (scanned >= 0) return scanned;
     const int counted = run_filter_rows(device, stream, f, indexVector, pred, n, p.a.length, virtualIdx, decoded);
     if (counted >= 0) return counted;
     // (-1: somebody's flush applied the vector's pending filters since the eligibility check: the ordinary filter below)
@@ -1823,7 +1897,8 @@ void hook_on_wait(int device, void *streamPtr) {
 // which still reads it (the value is the tag AresMemReleaseHeld will be called with)
 uintptr_t hook_on_free(int device, void *ptr, size_t bytes) {
   const ByteRange r = range_of(ptr, bytes);
-  grouped_note_write(device, ptr, bytes);
+  grouped_note_gone(device, ptr, bytes);
+  scan_ahead_note_touch(device, ptr, bytes, /*freed=*/true);
   uintptr_t hold = 0;
   ReleaseSet released;
   try {
@@ -1953,6 +2028,7 @@ void hook_on_access(int device, const void *ptr, size_t bytes) {
     // no longer be re-derived (queues that depended on the journal were launched above)
     for (auto it = t_state->journals.begin(); it != t_state->journals.end();)
       it = journal_touched(it->first, it->second, r, nullptr) ? t_state->journals.erase(it) : std::next(it);
+    scan_ahead_note_touch(device, ptr, bytes, /*freed=*/false);  // ... and a scan launched ahead of its HashReduce has read what is no longer there
   } catch (std::exception &e) {
     fprintf(stderr, "Exception happened when handling a device copy: %s\n", e.what());
   }
@@ -1990,6 +2066,7 @@ void hook_on_stream_destroy(int device, void *streamPtr) {
       }
       t_state->pending.erase(stream);
       t_state->expansions.erase(stream);
+      scan_ahead_stream_gone(device, stream);  // (the stream's hint, and the regions of a scan launched from it)
       auto lim = t_state->limbo.find(stream);
       if (lim != t_state->limbo.end()) drop_limbo(lim, nullptr);  // (the stream's tag is released below, whatever was held under it)
       for (auto it = t_state->journals.begin(); it != t_state->journals.end();)
@@ -2160,7 +2237,11 @@ bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const Dimensi
   {
     DeferLock lock(device);
     auto it = t_state->pending.find(stream);
-    if (it == t_state->pending.end() || it->second.jobs.count == 0) return false;
+    if (it == t_state->pending.end() || it->second.jobs.count == 0) {
+      // (nothing is pending — the batch's transforms were launched, or there were none: a scan launched at the filter goes unread)
+      if (scan_stash_take(device, stream)) scan_stash_settled(device, stream, kScanAheadDiscardAbandoned);
+      return false;
+    }
     PendingQueue &pq = it->second;
     bool ok = !forcedGlobal;
     // dimension slots of 4, 2 or 1 bytes, in the vector's (descending width) order
@@ -2185,12 +2266,14 @@ bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const Dimensi
     if (!ok) {  // the ordinary path: the pending work runs now, ahead of this call on the same stream
       launch_queue(stream, pq, /*inOrder=*/true);
       g_releaseHeld(device, hold_tag(stream));
+      if (scan_stash_take(device, stream)) scan_stash_settled(device, stream, kScanAheadDiscardPlan);  // (a scan launched at the filter goes unread)
       return false;
     }
     take_queue(pq, q);
   }
   DimensionVector prevKeys = in;
-  const int result = fused_hash_reduce_run(device, plan, n0, prevKeys, inValues, prev, out, outValues, a, stream);
+  // (the batch's scan as its last filter launched it from a hint, if it did: the run takes it for its own or drops it)
+  const int result = fused_hash_reduce_run(device, plan, n0, prevKeys, inValues, prev, out, outValues, a, stream, scan_stash_take(device, stream));
   DeferLock lock(device);
   if (result < 0) {  // a partition region overflowed, or the call was declined: materialise the inputs after all
     launch_queue(stream, q, /*inOrder=*/true);
@@ -2202,6 +2285,76 @@ bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const Dimensi
   *groups = result;
   return true;
 }
+
+// ---- scan at filter: the hint (AresHintFusedBatch) ---------------------------------------------------------------------------
+// The hinted plan is put together by the functions plan_from_queue uses, in its order, from the operands the batch's calls
+// will bind: what HashReduce derives from the stream's queue and journal is then equal field for field (fused_plan_equal)
+// whenever the calls arrive as hinted.  Anything that does not fit declines the hint: nothing is launched from it.
+namespace {
+// the operand of one hinted expression as the call that carries it will see it (run_transform / run_filter); false: not the hot shape
+bool hinted_operands(const AresFusedExpr &e, bool compareOnly, int batchRows, hipStream_t stream, FastOperands &f) {
+  if (e.arity != 1 && e.arity != 2) return false;
+  if (e.lhs.Type != VectorPartyInput || (e.arity == 2 && e.rhs.Type != ConstantInput)) return false;
+  if (static_cast<int64_t>(e.lhs.Vector.VP.Length) < batchRows) return false;  // (no speculative read may leave an allocation)
+  InputVector ins[2] = {e.lhs, e.arity == 2 ? e.rhs : e.lhs};
+  EvalParams p;
+  CallTemps temps;
+  build_params(ins, e.arity, stream, nullptr, nullptr, 0, e.functor, p, temps);
+  return p.a.length >= static_cast<uint32_t>(batchRows) && fast_operands(p, f, compareOnly) && f.step == 4;
+}
+bool hint_fused_batch(int device, hipStream_t stream, const AresFusedQuery &q, int batchRows, int prevSize, int measureBytes) {
+  if (!fuse_available() || !row_space_enabled() || !scan_at_filter_enabled()) return false;
+  if (q.numDims < 1 || q.numDims > kGenericFusedDims || q.numFilters < 1 || q.numFilters > kExtensionFilters) return false;
+  if (batchRows <= 0 || prevSize < 0 || static_cast<int64_t>(batchRows) + prevSize > INT32_MAX) return false;
+  if (measureBytes != 4 && measureBytes != 8) return false;
+  const int mt = q.measure.outType;
+  if (!(mt == Int32 || mt == Uint32 || mt == Float32 || mt == Int64 || mt == Float64) || measureBytes != ((mt == Int64 || mt == Float64) ? 8 : 4))
+    return false;
+  AggSpec a;
+  if (!supported_agg_spec(q.aggFunc, measureBytes, hash_reduce_lds_supported, &a)) return false;
+  ScanHint h;
+  memset(&h, 0, sizeof(h));
+  const int nd = q.numDims;
+  h.nd = nd;
+  h.batchRows = batchRows;
+  h.prevSize = prevSize;
+  auto note = [&](const FastOperands &f) {
+    column_ranges(f, static_cast<uint32_t>(batchRows), [&](const ByteRange &c) { h.ranges[h.numRanges++] = ScanHint::Range{c.lo, c.hi}; });
+  };
+  SinkD sink;
+  FastOperands f;
+  for (int d = 0; d < nd; d++) {
+    const int t = q.dims[d].outType;
+    if (!(t == Int32 || t == Uint32 || t == Float32) || !hinted_operands(q.dims[d], false, batchRows, stream, f)) return false;
+    memset(&sink, 0, sizeof(sink));
+    sink.type = SINK_DIM;
+    sink.dtype = t;
+    sink.width = 4;
+    fused_plan_dim(h.plan, d, f, sink, 4);
+    note(f);
+  }
+  if (!hinted_operands(q.measure, false, batchRows, stream, f)) return false;
+  memset(&sink, 0, sizeof(sink));
+  sink.type = SINK_MEASURE;
+  sink.dtype = mt;
+  sink.width = measureBytes;
+  sink.agg = q.aggFunc;
+  sink.identity = identity_bits(q.aggFunc, mt);
+  if (sink.agg == AGGR_AVG_FLOAT || (measureBytes == 8 && sink.identity != 0)) return false;
+  fused_plan_measure(h.plan, nd, f, sink, measureBytes);
+  note(f);
+  for (int k = 0; k < q.numFilters; k++) {
+    if (!hinted_operands(q.filters[k], true, batchRows, stream, f)) return false;
+    f.idx = nullptr;  // (as the journal keeps them)
+    h.filters[k] = f;
+    note(f);
+  }
+  if (!fused_plan_filters(h.plan, h.filters, static_cast<size_t>(q.numFilters))) return false;
+  if (h.plan.numCols > nd + 2 || fused_plan_narrow(h.plan, nd)) return false;
+  scan_hint_set(device, stream, h);
+  return true;
+}
+}  // namespace
 
 // ---- Sort + Reduce over pending transforms (sort_reduce_fused.hip) ---------------------------------------------------------
 namespace {
@@ -2553,10 +2706,25 @@ void AresFlushDeferred(int device) {
   }
 }
 
+void AresHintFusedBatch(const AresFusedQuery *query, int batchRows, int prevSize, int measureBytes, void *cudaStream, int device) {
+  bool taken = false;
+  try {  // (a hint has no result: whatever goes wrong with it, the batch runs as if it had not been given)
+    taken = query != nullptr && device >= 0 && device < kMaxDevices &&
+            hint_fused_batch(device, reinterpret_cast<hipStream_t>(cudaStream), *query, batchRows, prevSize, measureBytes);
+  } catch (std::exception &) {
+  }
+  if (!taken) scan_ahead_count(kScanAheadDeclined);
+}
+
+void AresScanAtFilterStats(unsigned long long *counters) {
+  if (counters) scan_ahead_stats(counters);
+}
+
 CGoCallResHandle InitIndexVector(uint32_t *indexVector, uint32_t start, int indexVectorLength, void *cudaStream,
                                  int device) {
   ARES_ABI_BEGIN_NOFLUSH(device)
   hipStream_t stream = reinterpret_cast<hipStream_t>(cudaStream);
+  scan_hint_init_index(device, stream);  // (the hinted batch begins — or it is over, and so is the hint)
   begin_batch(device, stream, indexVector, start, indexVectorLength);
   if (!defer_iota(device, stream, indexVector, start, indexVectorLength)) {
     flush_deferred(device);

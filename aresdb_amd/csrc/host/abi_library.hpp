@@ -58,6 +58,8 @@ struct AbiLibrary {
   decltype(&::Reduce) Reduce;
   decltype(&::HashReduce) HashReduce;
   decltype(&::AresFusedFilterHashReduce) FusedFilterHashReduce = nullptr;  // optional extension
+  decltype(&::AresHintFusedBatch) HintFusedBatch = nullptr;                // optional extension: the batch's plan, said before its filters
+  decltype(&::AresScanAtFilterStats) ScanAtFilterStats = nullptr;          // ... and what became of the hints
   decltype(&::AresFusedFilterSelect) FusedFilterSelect = nullptr;          // optional extension
   decltype(&::AresFusedFilterJoinSelect) FusedFilterJoinSelect = nullptr;  // optional extension
   decltype(&::AresJoinColumnsRun) JoinColumnsRun = nullptr;                // optional extension, with ...
@@ -114,6 +116,8 @@ struct AbiLibrary {
     bind(algoHandle, "WriteGeoShapeDim", WriteGeoShapeDim);
     bind(algoHandle, "Expand", Expand);
     bind(algoHandle, "AresFusedFilterHashReduce", FusedFilterHashReduce, true);
+    bind(algoHandle, "AresHintFusedBatch", HintFusedBatch, true);
+    bind(algoHandle, "AresScanAtFilterStats", ScanAtFilterStats, true);
     bind(algoHandle, "AresFusedFilterSelect", FusedFilterSelect, true);
     bind(algoHandle, "AresFusedFilterJoinSelect", FusedFilterJoinSelect, true);
     bind(algoHandle, "AresJoinColumnsRun", JoinColumnsRun, true);

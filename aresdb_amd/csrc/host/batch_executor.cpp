@@ -491,22 +491,38 @@ bool AresQuery::fusedDims(AresFusedExpr *out, int *count, int *joins) {
   return true;
 }
 
-// returns false when this batch must take the ordinary sequence
-bool AresQuery::runBatchFused(const VectorPartySlice *cols, int ncols, int n) {
+// The running batch (`columns` are bound) as the one-call extension and the hint take it; false: a plan neither fits
+bool AresQuery::fusedQuery(AresFusedQuery *q) {
   const Plan &p = *batchPlan;
-  if (!p.useFusedExtension || !p.useHashReduction || fusedDeclined || !lib->FusedFilterHashReduce) return false;
-  if (p.hasGeo || p.isHLL()) return false;
+  if (!p.useHashReduction || p.hasGeo || p.isHLL()) return false;
   if (!p.foreign.empty() || !p.foreignFilters.empty() || baseCounts) return false;
   if (p.dimNodes.empty() || p.dimNodes.size() > 4 || p.filters.size() > 4) return false;
-  columns = cols;
-  numColumns = ncols;
-  Pod<AresFusedQuery> q;
   if (!fusedFilters(p.filters, q->filters, &q->numFilters)) return false;
   for (int t : p.dimTypes)  // (all 4 bytes wide: vector order == query order)
     if (data_type_bytes(t) != 4) return false;
   if (!fusedDims(q->dims, &q->numDims)) return false;
   if (!fusedExpr(p.measureNode, p.measureType, &q->measure)) return false;
   q->aggFunc = static_cast<AggregateFunction>(p.aggFunc);
+  return true;
+}
+
+// The batch takes the ordinary sequence: the library is told beforehand what that sequence will be (AresHintFusedBatch), so
+// that it may count the last filter with the batch's fused scan.  A hint only: nothing the batch does depends on it.
+void AresQuery::hintBatch() {
+  if (!lib->HintFusedBatch || batchPlan->filters.empty()) return;
+  Pod<AresFusedQuery> q;
+  if (!fusedQuery(&*q)) return;
+  lib->HintFusedBatch(&q.get(), batchRows, resultSize, batchPlan->measureBytes(), stream, device);
+}
+
+// returns false when this batch must take the ordinary sequence
+bool AresQuery::runBatchFused(const VectorPartySlice *cols, int ncols, int n) {
+  const Plan &p = *batchPlan;
+  if (!p.useFusedExtension || fusedDeclined || !lib->FusedFilterHashReduce) return false;
+  columns = cols;
+  numColumns = ncols;
+  Pod<AresFusedQuery> q;
+  if (!fusedQuery(&*q)) return false;
   size = n;
   prepareForDimAndMeasureEval();  // result buffers sized for resultSize + n, previous results carried over
   calls++;
@@ -609,6 +625,7 @@ void AresQuery::runBatch(const VectorPartySlice *cols, int ncols, int n, uint32_
     return;
   }
   prepareForFiltering(cols, ncols, n, bc, start);
+  hintBatch();
   preExec();
   filter();
   join();

@@ -172,6 +172,8 @@ struct AresQuery {
   bool fusedExpr(int nodeIdx, int outType, AresFusedExpr *e, int *join = nullptr);
   bool fusedFilters(const std::vector<int> &roots, AresFusedExpr *out, int *count, int *joins = nullptr);
   bool fusedDims(AresFusedExpr *out, int *count, int *joins = nullptr);
+  bool fusedQuery(AresFusedQuery *q);
+  void hintBatch();
   bool runBatchFused(const VectorPartySlice *cols, int ncols, int n);
   bool runBatchFusedSelect(const VectorPartySlice *cols, int ncols, int n);
 

@@ -179,6 +179,30 @@ CGoCallResHandle AresFusedFilterHashReduce(const AresFusedQuery *query, int batc
                                            uint8_t *prevValues, int prevSize, DimensionVector outKeys,
                                            uint8_t *outValues, void *cudaStream, int device);
 
+/* Scan at filter: a HINT for hosts that keep the one-call-per-node sequence.  Called before a batch's filters (after the
+ * batch's columns are in place, before or after InitIndexVector's buffers exist: no buffer of the sequence is named) it says
+ * what the stream's next
+ *   InitIndexVector, BinaryFilter x numFilters, Unary/BinaryTransform x (numDims + 1), HashReduce
+ * sequence will be: `query` as AresFusedFilterHashReduce takes it, bound to THIS batch's columns; batchRows; prevSize = the
+ * query's current result size; measureBytes = the width of the measure vector (4 or 8).  When the sequence then arrives as
+ * hinted, its last filter is counted by the batch's fused scan itself, launched in the filter kernel's place — the scan
+ * evaluates the filters per row anyway — and HashReduce merges what that scan wrote instead of scanning: one kernel and one
+ * pass over the last filter's column less per batch.  No ABI call changes its arguments, its result or what it leaves in any
+ * buffer the host can read; a sequence that differs from the hint (another filter follows, other columns, another prevSize,
+ * a column written in between, no HashReduce at all) is executed as ever and only costs the scan that was launched for
+ * nothing; after two such scans in a row the stream's hints are ignored until one describes another shape.
+ * The hint ends with the InitIndexVector after the next one, with the stream, and with any write to or free of a byte of a
+ * hinted column.  It is declined without effect when a column is shorter than batchRows, when the shape is not one the
+ * compact DIRECT scan takes (1-4 dimensions of 4 bytes, a 4-byte main-table column each, at most 4 comparison filters), and
+ * when ARES_DEFER=0, ARES_FUSE=0, ARES_FILTER_ROWSPACE=0 or ARES_SCAN_AT_FILTER=0 is set (the last obeys AresReloadEnv).
+ * counters receives 10 words since the process started: {hints taken, scans launched at a filter, scans HashReduce merged its result from,
+ * hints declined, scans discarded because HashReduce derived another plan, ... other sizes / partitions / kernel / stream
+ * room or needed region A, ... a hinted column was written or freed, ... HashReduce never consumed the stream's queue,
+ * scans taken whose call then scanned again or fell back (stale ranges, record stream overflow), hints ignored by the
+ * two-discard latch}: every scan launched at a filter ends in exactly one of the counters behind "scans launched". */
+void AresHintFusedBatch(const AresFusedQuery *query, int batchRows, int prevSize, int measureBytes, void *cudaStream, int device);
+void AresScanAtFilterStats(unsigned long long *counters);
+
 /* Fused select scan: the batch of a NON-AGGREGATION query (SELECT cols WHERE ... LIMIT n, query/aql_nonaggr_batchexecutor.go)
  * in one limit-aware pass over the source columns.  It replaces, for one batch, the call sequence
  *   InitIndexVector, Unary/BinaryFilter x numFilters, Unary/BinaryTransform x numDims into rows [0, survivors) of outKeys
