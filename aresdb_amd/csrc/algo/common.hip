@@ -211,8 +211,8 @@ void evict_oldest_cached(size_t bound) {
   }
 }
 
-void (*g_memNoteActivity)() = nullptr;  // AresMemNoteActivity of the sibling libmem.so (transform.hip resolves it)
-void (*g_memNoteWrite)(int, const void *, size_t) = nullptr;  // AresMemNoteWrite of the sibling libmem.so (transform.hip resolves it)
+void (*g_memNoteActivity)() = nullptr;  // AresMemNoteActivity of the sibling libmem.so (deferral.hip resolves it)
+void (*g_memNoteWrite)(int, const void *, size_t) = nullptr;  // AresMemNoteWrite of the sibling libmem.so (deferral.hip resolves it)
 int current_device() {
   int device = 0;
   (void)hipGetDevice(&device);
@@ -240,7 +240,7 @@ void mem_note_vector_all(int device, const DimensionVector &v) {
   if (v.HashValues) g_memNoteWrite(device, v.HashValues, 8 * cap);
   if (v.IndexVector) g_memNoteWrite(device, v.IndexVector, 4 * cap);
 }
-void (*g_memTrimCache)(int) = nullptr;  // AresMemTrimCache of the sibling libmem.so (transform.hip resolves it)
+void (*g_memTrimCache)(int) = nullptr;  // AresMemTrimCache of the sibling libmem.so (deferral.hip resolves it)
 
 // A stream is being destroyed (the host has synchronised it): its cached temporaries become the device's —
 // the Go host creates and destroys two streams per query, blocks cached under dead handles would only pile up,
@@ -251,7 +251,7 @@ void stream_cache_purge(int device, hipStream_t stream) {
   // the blocks kept and blamed the reuse; round 4 traced them to the HIP runtime being handed events of destroyed
   // streams (libmem's fences, the lazy compactions' error words) — a use after free inside the runtime that the
   // device-wide synchronisation of hipFree merely made unlikely.  Those events now die with their stream
-  // (mem/memory.hip FenceEvent, transform.hip hook_on_stream_destroy; profiles/r4_race_hunt.md).
+  // (mem/memory.hip FenceEvent, deferral_hooks.hip hook_on_stream_destroy; profiles/r4_race_hunt.md).
   static const bool keep = [] {
     const char *e = getenv("ARES_TEMP_ORPHANS");
     return !(e && e[0] == '0');

@@ -71,16 +71,16 @@ inline void check_launch(const char *what) {
   hip_check(hipGetLastError(), what);
 }
 
-// launches the transforms held back for cross-call fusion on `device` (transform.hip)
+// launches the transforms held back for cross-call fusion on `device` (deferral.hip)
 void flush_deferred(int device);
-// second-stage fusion (transform.hip, include/ares_extensions.h)
+// second-stage fusion (fused_consumers.hip, include/ares_extensions.h)
 bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const DimensionVector &in, const uint8_t *inValues,
                                    const DimensionVector &out, uint8_t *outValues, int valueBytes, int length, int aggFunc,
                                    int *groups);
 void invalidate_filter_journal(int device, const uint32_t *indexVector);
 // ARES_HASH_REDUCE=global: every HashReduce takes the global-table path (hash_reduce.hip)
 bool global_table_forced();
-// true when the sibling libmem.so reports waits, frees and copies to this library (transform.hip)
+// true when the sibling libmem.so reports waits, frees and copies to this library (deferral.hip)
 bool deferral_hooks_active();
 // something writes (or frees) [ptr, ptr + bytes): partition-grouped results that overlap are no longer
 // trusted (hash_reduce_lds.hip)
@@ -98,7 +98,7 @@ void flush_deferred_for_vector(int device, const DimensionVector &v, const void 
 // skipped work whose outputs lie in ranges that are about to be overwritten is dropped, never launched
 void drop_skipped_outputs(int device, const void *a, size_t aBytes, const void *b, size_t bBytes);
 
-// ---- lazy fills (transform.hip): buffers defined as a repeated 4- or 8-byte pattern that nobody has written yet ----
+// ---- lazy fills (deferral.hip): buffers defined as a repeated 4- or 8-byte pattern that nobody has written yet ----
 // false = deferral is off (no sibling libmem.so hooks): the caller writes the bytes itself
 bool defer_fill(int device, hipStream_t stream, void *dst, size_t bytes, uint64_t pattern, int unit);
 bool pending_fill_exact(int device, const void *dst, size_t bytes, uint64_t *pattern, int *unit);
@@ -120,7 +120,7 @@ void temp_stats(size_t *handedOut, size_t *cached);
 
 // The stream of the entry point the calling thread is executing.  Work that was DEFINED on another stream (a lazy
 // fill, a lazy iota, a lazy compaction) and is written on that stream at one of this call's flush points is waited for
-// before the call's own kernels — which run on this stream — read it (transform.hip: order_before_caller).  Calls
+// before the call's own kernels — which run on this stream — read it (deferral.hip: order_before_caller).  Calls
 // that arrive from libmem.so (copies, frees) have no stream here: they wait for whatever they launch.
 struct CallStream {
   hipStream_t stream;

@@ -1,4 +1,4 @@
-// Shared by the fast transform / filter kernels (transform.hip) and the fused scan of
+// Shared by the fast transform / filter kernels (transform_kernels.hpp, deferral_kernels.hpp) and the fused scan of
 // hash_reduce_lds.hip: the "4-byte column (x constant)" operand shape, its evaluation and the host
 // code that recognises it.
 #pragma once

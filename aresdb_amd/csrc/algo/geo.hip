@@ -8,7 +8,7 @@
 // register broadcasts (see geo_intersect_kernel); the crossing parity accumulates in registers (up
 // to 8 words = 256 shapes): no atomics, no LDS, one read-modify-write of the predicate words per
 // entry.  The same pass writes a keep byte per entry; the index vector and the RecordID vectors are
-// then compacted by the filter's chain-free compaction kernels (transform.hip).
+// then compacted by the filter's chain-free compaction kernels (compact_by_predicate, deferral.hip).
 #include <hip/hip_runtime.h>
 
 #include <cfloat>

@@ -626,7 +626,7 @@ int hash_reduce_lds(int device, const DimensionVector &inputKeys, const uint8_t 
 }
 
 // The fused pipeline for an already built plan (shared by the extension entry point and by the
-// in-ABI fusion of pending transforms into HashReduce, transform.hip).  Returns the number of groups
+// in-ABI fusion of pending transforms into HashReduce, fused_consumers.hip).  Returns the number of groups
 // or -1 when a region overflowed.
 static void fused_note_first_batch(size_t shape, int groups) {
   if (!shape || groups < 0) return;

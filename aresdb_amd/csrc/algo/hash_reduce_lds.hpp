@@ -106,7 +106,7 @@ inline bool fused_plan_narrow(const FusedPlanD &p, int nd) {
 
 // ---- building a plan ------------------------------------------------------------------------------------------------
 // One copy of each decision for everybody who writes a FusedPlanD: the two fusions over a stream's pending work
-// (transform.hip), the fused extension (hash_reduce_lds.hip) and the vector-sourced launcher (hr_rtc.hip).  The struct is
+// (fused_consumers.hip), the fused extension (hash_reduce_lds.hip) and the vector-sourced launcher (hr_rtc.hip).  The struct is
 // memset to zero first; the spec makers (hr_rtc_gen.hpp) and the launches read it field by field.
 inline FusedColumn fused_column_of(const FastOperands &f) { return FusedColumn{f.vals, f.nulls, f.bitOff, static_cast<uint32_t>(f.step ? f.step : 4)}; }
 // the expression without what belongs to one launch (the column lives in its slot, the rows come from the scan)
@@ -213,7 +213,7 @@ int fused_hash_reduce_run(int device, const FusedPlanD &plan, int batchRows, con
                           const uint8_t *prevValues, int prevSize, const DimensionVector &outKeys, uint8_t *outValues,
                           const AggSpec &a, hipStream_t stream, std::shared_ptr<ScanStash> stash = nullptr);
 
-// ---- scan at filter (hash_reduce_lds.hip; the filter call itself: transform.hip) ----------------------------------------
+// ---- scan at filter (hash_reduce_lds.hip; the filter call itself: transform.hip; the hint: fused_consumers.hip)
 // What AresHintFusedBatch said about a stream's next InitIndexVector ... HashReduce sequence.
 struct ScanHint {
   FusedPlanD plan;  // built like plan_from_queue builds HashReduce's: fused_plan_dim x nd, fused_plan_measure, fused_plan_filters

@@ -322,7 +322,7 @@ struct ExprConst {
   DVal y;
   FastDivisor fd;
 };
-__device__ __forceinline__ ExprConst expr_const(const FastOperands &f) {  // as store_tile (transform_kernels.hpp) prepares them
+__device__ __forceinline__ ExprConst expr_const(const FastOperands &f) {  // as store_tile (deferral_kernels.hpp) prepares them
   ExprConst c;
   c.y.bits = f.bbits;
   c.y.ok = f.bok;

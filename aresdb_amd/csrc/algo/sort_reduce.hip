@@ -935,7 +935,7 @@ static int expand_impl(const DimensionVector &in, const DimensionVector &out, ui
 // Every row is the empty dimension row: Sort gives all of them one constant hash and leaves the index vector as
 // it was, Reduce folds the whole value vector into ONE group.  Nothing of that needs 8 + 4 bytes per row of hash
 // and index traffic, an 8-pass radix sort or a segmented reduction:
-//   * Sort over an index vector that is still a lazy iota defines the hash vector as a lazy fill (transform.hip)
+//   * Sort over an index vector that is still a lazy iota defines the hash vector as a lazy fill (fused_consumers.hip, deferral.hip)
 //     and returns: no kernel;
 //   * Reduce then knows the hashes are equal and the index is the identity: one reduction pass over the value rows
 //     that exist — and the rows a constant measure transform only DEFINED (COUNT(*): the literal 1) are added

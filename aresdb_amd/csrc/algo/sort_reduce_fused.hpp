@@ -1,5 +1,5 @@
 // Sort + Reduce without sorting rows: the hash-keyed group-by behind the reference's default aggregation path
-// (sort_reduce_fused.hip; host-side deferral: transform.hip "lazy sorts").
+// (sort_reduce_fused.hip; host-side deferral: fused_consumers.hip "lazy sorts").
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -20,7 +20,7 @@ bool fused_sort_reduce_supported(const AggSpec &a);
 // surviving row carries the value pattern `constBits`).  Writes the groups — ascending 64-bit row hash, dimension row of
 // the lowest-indexed row, aggregated value — to rows [0, groups) of `out` / `outValues` (strided by in.VectorCapacity, as
 // the reference: query/sort_reduce.cu:234-239) and returns their number.  out.IndexVector, in.HashValues and
-// in.IndexVector are NOT written (the caller keeps them defined: transform.hip).
+// in.IndexVector are NOT written (the caller keeps them defined: fused_consumers.hip).
 // kFusedUnavailable: declined before anything was launched; -1: launched, outputs possibly part-written, take the real
 // Sort + Reduce (a partition's table or record stream overflowed, a row hash equals the table's empty word).
 int fused_sort_reduce_run(int device, const FusedPlanD &plan, int nd, bool constMeasure, uint64_t constBits, int batchRows,
@@ -40,7 +40,7 @@ void sorted_state_note_write(int device, const void *ptr, size_t bytes);
 void sort_keys_now(const DimensionVector &keys, int length, hipStream_t stream);
 int reduce_now(const DimensionVector &in, uint8_t *inputValues, const DimensionVector &out, uint8_t *outputValues, int valueBytes,
                int length, int aggFunc, hipStream_t stream);
-// transform.hip: Sort over rows whose transforms are still pending is DEFINED, not run (true = nothing left to do) ...
+// fused_consumers.hip: Sort over rows whose transforms are still pending is DEFINED, not run (true = nothing left to do) ...
 bool define_lazy_sort(int device, hipStream_t stream, const DimensionVector &keys, int length);
 // ... or, when the rows exist (written by kernels): asked BEFORE Sort's flush (the index vector's lazy iota is kept from being
 // written), defined AFTER it (false: the index vector has been written, the caller sorts)

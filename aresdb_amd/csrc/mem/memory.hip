@@ -97,7 +97,7 @@ inline void mem_trace_alloc(size_t bytes, size_t rounded, const char *source, si
   } while (0)
 
 // libalgorithm.so may hold transforms it has accepted but not launched yet (cross-call fusion,
-// aresdb_amd/csrc/algo/transform.hip); it registers a hook here, and every entry point through
+// aresdb_amd/csrc/algo/deferral.hip, deferral_hooks.hip); it registers a hook here, and every entry point through
 // which the host could observe, free or overwrite device memory runs it first.
 typedef void (*FlushHook)(int device);
 std::atomic<FlushHook> g_flushHook{nullptr};
