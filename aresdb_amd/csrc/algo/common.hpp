@@ -73,6 +73,8 @@ inline void check_launch(const char *what) {
 
 // launches the transforms held back for cross-call fusion on `device` (deferral.hip)
 void flush_deferred(int device);
+// scratch frames that were defined as constant chains instead of being written (deferral.hpp: FrameDef) are written now
+void materialize_all_frames(int device);
 // second-stage fusion (fused_consumers.hip, include/ares_extensions.h)
 bool fuse_pending_into_hash_reduce(int device, hipStream_t stream, const DimensionVector &in, const uint8_t *inValues,
                                    const DimensionVector &out, uint8_t *outValues, int valueBytes, int length, int aggFunc,
@@ -153,7 +155,8 @@ class CallStreamScope {
 
 #define ARES_ABI_BEGIN(device)     \
   ARES_ABI_BEGIN_NOFLUSH(device)   \
-  ares::flush_deferred(device);
+  ares::flush_deferred(device);    \
+  ares::materialize_all_frames(device); /* (does not say what it reads: scratch frames defined as chains are written) */
 
 #define ARES_ABI_END(name)                                            \
   }                                                                   \

@@ -285,6 +285,81 @@ void launch_queue(hipStream_t stream, PendingQueue &q, bool inOrder) {
   if (syncAfter) t_syncAfterUnlock.push_back(stream);  // (DeferLock: after the mutex is released)
 }
 
+// ---- scratch frames defined as constant chains --------------------------------------------------------------------------
+// ARES_CHAINS=0: no frame is ever defined — every inner node launches its own kernel, as before there were chains
+bool chains_enabled() {
+  static EnvSwitch<bool> on("ARES_CHAINS", [](const char *e) { return !(e && e[0] == '0'); });
+  return on.get() && fuse_available();
+}
+bool frame_writes_touch(const FrameDef &d, const ByteRange &r) {
+  return range_of(d.s.values, 4ull * d.n).overlaps(r) || range_of(d.s.nulls, static_cast<size_t>(d.n)).overlaps(r);
+}
+bool frame_reads_touch(const FrameDef &d, const ByteRange &r) {
+  return column_overlaps(d.f, d.colRows, r) || (d.idxVec && range_of(d.idxVec, 4ull * d.n).overlaps(r));
+}
+// caller holds the device's DeferLock and has selected the device: the frame is written now — what the defining calls would
+// have left in it — on the stream it was defined on, behind the compaction (or the iota) of the index vector it reads
+std::map<uint8_t *, FrameDef>::iterator materialize_frame(std::map<uint8_t *, FrameDef>::iterator it) {
+  const FrameDef d = it->second;
+  it = t_state->frames.erase(it);  // (the entry goes first: nothing below finds it again)
+  if (d.f.idx) {
+    run_compaction(d.f.idx);
+    auto io = t_state->iotas.find(const_cast<uint32_t *>(d.f.idx));
+    if (io != t_state->iotas.end()) write_iota(io);
+  }
+  mem_note_write(t_state->device, d.s.values, 4ull * static_cast<size_t>(d.n));
+  mem_note_write(t_state->device, d.s.nulls, static_cast<size_t>(d.n));
+  launch_fast_transform(d.f, d.s, d.n, d.stream);
+  if (d.overWait) t_syncAfterUnlock.push_back(d.stream);  // the host believes the stream idle
+  else order_before_caller(d.stream);
+  return it;
+}
+void materialize_frames(const ByteRange *r, bool readsToo) {
+  for (auto it = t_state->frames.begin(); it != t_state->frames.end();) {
+    const bool hit = !r || frame_writes_touch(it->second, *r) || (readsToo && frame_reads_touch(it->second, *r));
+    if (hit) {
+      materialize_frame(it);
+      it = t_state->frames.begin();  // (the compaction it ran first may have touched the map's neighbours: start over)
+    } else {
+      ++it;
+    }
+  }
+}
+// the index vector is about to mean something else (a filter compacts it, InitIndexVector redefines it)
+void materialize_frames_of_index(const uint32_t *indexVector) {
+  for (auto it = t_state->frames.begin(); it != t_state->frames.end();) {
+    if (indexVector && it->second.idxVec == indexVector) {
+      materialize_frame(it);
+      it = t_state->frames.begin();
+    } else {
+      ++it;
+    }
+  }
+}
+void settle_frames_for_write(const ByteRange &r) {
+  for (auto it = t_state->frames.begin(); it != t_state->frames.end();) {
+    const FrameDef &d = it->second;
+    const ByteRange v = range_of(d.s.values, 4ull * d.n), nb = range_of(d.s.nulls, static_cast<size_t>(d.n));
+    if (frame_reads_touch(d, r)) {
+      materialize_frame(it);
+      it = t_state->frames.begin();
+    } else if (!v.overlaps(r) && !nb.overlaps(r)) {
+      ++it;
+    } else if (r.lo <= v.lo && v.hi <= r.hi) {  // the values are overwritten whole (validity bytes follow their values): retired
+      it = t_state->frames.erase(it);
+    } else {
+      materialize_frame(it);
+      it = t_state->frames.begin();
+    }
+  }
+}
+// for the entry points that do not say what they read (ARES_ABI_BEGIN): every frame of the device is written
+void materialize_all_frames(int device) {
+  if (!defer_available()) return;
+  DeferLock lock(device);
+  if (!t_state->frames.empty()) materialize_frames(nullptr, false);
+}
+
 // caller holds the device's DeferLock.  Launches the skipped transforms of every limbo entry of the device
 // (range == nullptr) or of those whose outputs overlap `range`, and forgets the entries.
 bool materialize_limbo(const ByteRange *range, ReleaseSet *released) {
@@ -595,6 +670,12 @@ void flush_deferred_impl(int device, const ByteRange *limboA, const ByteRange *l
   // measure / hash vectors, which only Sort, Reduce, HashReduce, Expand, HyperLogLog and copies look at
   if (limboA) materialize_fills(limboA);
   if (limboB) materialize_fills(limboB);
+  // scratch frames defined as constant chains likewise: written for the bytes the caller names (their own, or — the caller
+  // may be about to rewrite them — their sources), left alone by everybody else
+  if (!t_state->frames.empty()) {
+    if (limboA) materialize_frames(limboA, true);
+    if (limboB) materialize_frames(limboB, true);
+  }
   for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();) {
     const ByteRange v = range_of(it->first, 4ull * it->second.n);
     const bool wanted = !it->second.consumed || (limboA && v.overlaps(*limboA)) || (limboB && v.overlaps(*limboB));
@@ -687,6 +768,7 @@ void begin_batch(int device, hipStream_t stream, const uint32_t *indexVector, ui
       drop_limbo(lim, nullptr);
       release = true;
     }
+    if (!t_state->frames.empty()) materialize_frames_of_index(indexVector);  // (frames defined over the vector's old contents)
     t_state->compactions.erase(indexVector);  // the vector is redefined
     t_state->expansions.erase(stream);  // (what still reads a decoded column keeps it alive itself)
     trace_decoded_columns_held(*t_state);

@@ -30,6 +30,24 @@
 //                                 (sort_reduce_fused.hip) and leaves its own (`reduced`: the input's hash and index vector
 //                                 and the output's index vector are what a replay — skipped transforms, Sort, Reduce —
 //                                 would write: materialize_sort).
+//   * frames[first byte]          a 4-byte scratch frame DEFINED as a constant chain over one column (FrameDef): an inner node
+//                                 of the hot shape — `column (op) constant`, or `a defined frame (op) constant` — is recorded,
+//                                 not launched, and nothing else that is pending is flushed for it.  A following BinaryTransform
+//                                 `that frame (op) constant` composes: into a scratch sink a new definition, into a dimension or
+//                                 measure sink an ordinary queued job whose reads are the COLUMN's (compose_frame).  The exits of
+//                                 a definition, each one the only thing that happens to it there:
+//                                   - composed: it stays (the frame may have other readers);
+//                                   - written (materialize_frame: one transform_fast_kernel with the chain, on the defining stream,
+//                                     ordered before the reader — I1): a transform or filter that is handed the frame and does not
+//                                     compose (settle_frames_for_call), a copy (hook_on_access), an entry point that names the
+//                                     bytes it reads (flush_deferred_for_inputs), an entry point that does not say what it reads
+//                                     (ARES_ABI_BEGIN: materialize_all_frames), a filter or InitIndexVector over its index vector,
+//                                     a write to its source column or index vector, a free of them the host has not waited for;
+//                                   - retired without a launch: overwritten whole by a transform (a new definition included),
+//                                     freed (hook_on_free), its stream destroyed (hook_on_stream_destroy) — I2 - I4;
+//                                   - never launched by anything else: a flush from an unrelated call, launch_queue, a stream
+//                                     wait (I6) — a source column freed after the host waited is held for it, as for a queue.
+//                                 ARES_CHAINS=0 (or ARES_DEFER=0) defines none: every node runs the kernel it always ran.
 // Invariants (each one is what a reader of device memory relies on; the sequence fuzzer reads every buffer at random
 // points and the soak test does so from four threads):
 //   I1  Before ANY byte of device memory is read by something other than the consumer a definition was made for — a copy
@@ -85,6 +103,12 @@ inline bool column_overlaps(const FastOperands &f, uint32_t colRows, const ByteR
   bool hit = false;
   column_ranges(f, colRows, [&](const ByteRange &c) { hit = hit || c.overlaps(r); });
   return hit;
+}
+// one of the ranges `v` overlaps the operand's column
+inline bool column_ranges_touch(const std::vector<ByteRange> &v, const FastOperands &f, uint32_t colRows) {
+  for (const ByteRange &x : v)
+    if (column_overlaps(f, colRows, x)) return true;
+  return false;
 }
 inline bool touches(const std::vector<ByteRange> &v, const ByteRange &r) {
   for (const ByteRange &x : v)
@@ -322,6 +346,20 @@ struct ErrorCheck {
   std::shared_ptr<StreamBuffer> ws;  // keeps the error word alive until the copy has run
 };
 
+// A 4-byte scratch frame defined as a constant chain over one column and not written (see `frames` above)
+struct FrameDef {
+  hipStream_t stream;
+  FastOperands f;        // the column, the chain and — as its functor — the frame's own node: what a launch evaluates.  f.idx: the
+                         // index vector a launch reads (null: rows = positions)
+  SinkD s;               // the frame: values, validity bytes (values + nulls offset), dtype
+  int n;                 // rows
+  const uint32_t *idxVec;  // the index vector the defining call was handed (f.idx is null where it was a virtual iota)
+  uint32_t colRows;      // rows of the source column
+  std::shared_ptr<StreamBuffer> keep;  // the decoded copy of a run-length column the chain reads (or null)
+  bool overWait = false;  // the host has waited for the stream since (hook_on_wait): a freed source block is held, not raced
+  bool held = false;      // ... and one was
+};
+
 // Everything in here belongs to ONE device (`device`): entries are only ever made under a DeferLock of that device, so
 // nothing below carries a device number of its own.
 struct DeferState {
@@ -337,6 +375,7 @@ struct DeferState {
   std::map<uint8_t *, PendingFill> fills;  // by first byte; ranges never overlap
   std::map<const uint32_t *, PendingSort> sorts;  // by index vector
   std::map<hipStream_t, std::vector<RunExpansion>> expansions;  // decoded run-length columns of the stream's batch
+  std::map<uint8_t *, FrameDef> frames;  // scratch frames defined as constant chains, by first byte; ranges never overlap
   std::vector<ErrorCheck> errorChecks;
   std::vector<uint32_t *> errorSlots;  // recycled pinned words
   bool errorSeen = false;              // a check that was settled outside an entry point failed: the next poll reports it
@@ -375,8 +414,16 @@ void run_compaction(const uint32_t *idx);
 bool compaction_touches(const PendingCompact &c, const ByteRange &r);
 void forget_run_expansions(const ByteRange &r);
 void journal_count(const uint32_t *indexVector, int count);
+// scratch frames defined as constant chains (caller holds the device's DeferLock)
+bool frame_writes_touch(const FrameDef &d, const ByteRange &r);  // the frame's own bytes
+bool frame_reads_touch(const FrameDef &d, const ByteRange &r);   // its source column, its index vector
+std::map<uint8_t *, FrameDef>::iterator materialize_frame(std::map<uint8_t *, FrameDef>::iterator it);
+void materialize_frames(const ByteRange *r, bool readsToo);  // those whose bytes (readsToo: or sources) overlap r; null: all
+void materialize_frames_of_index(const uint32_t *indexVector);
+void settle_frames_for_write(const ByteRange &r);  // inside r: retired; cut by r, or reading r: written first
 // ... and what transform.hip's calls use; these take the lock themselves where they need it
 void flush_deferred_impl(int device, const ByteRange *limboA, const ByteRange *limboB, const uint32_t *exempt = nullptr);
+bool chains_enabled();  // ARES_CHAINS (on unless 0) and deferral with its hooks
 void begin_batch(int device, hipStream_t stream, const uint32_t *indexVector, uint32_t start, int n);
 void journal_filter(int device, const uint32_t *indexVector, const FastOperands *f, uint32_t colRows, int rowsBefore,
                     std::shared_ptr<StreamBuffer> keep = nullptr);

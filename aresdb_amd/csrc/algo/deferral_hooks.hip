@@ -44,6 +44,8 @@ void hook_on_wait(int device, void *streamPtr) {
     for (auto it = t_state->iotas.begin(); it != t_state->iotas.end();) {
       it = (it->second.stream == stream && !it->second.consumed) ? write_iota(it) : std::next(it);  // (not consumed: no Sort over it)
     }
+    for (auto &kv : t_state->frames)  // a frame nobody has read stays defined: its sources are inputs of pending work from now on
+      if (kv.second.stream == stream) kv.second.overWait = true;
     for (auto &kv : t_state->pending) {
       if (kv.first != stream || kv.second.jobs.count == 0 || kv.second.overWait) continue;
       PendingQueue &q = kv.second;
@@ -86,6 +88,33 @@ uintptr_t hook_on_free(int device, void *ptr, size_t bytes) {
     }
     erase_if(t_state->iotas, [&](auto &io) { return range_of(io.first, 4ull * io.second.n).overlaps(r); });  // an index vector nobody has read yet
     retire_fills(r, true);  // lazy fills of the block die unwritten
+    // scratch frames defined as constant chains: a frame of the block dies unwritten; one that READS the block is treated like
+    // a queued job that does — the block is held where the host has waited for the stream, the frame is written now otherwise
+    for (auto it = t_state->frames.begin(); it != t_state->frames.end();) {
+      FrameDef &d = it->second;
+      if (frame_writes_touch(d, r)) {
+        const hipStream_t s = d.stream;
+        const bool held = d.held;
+        it = t_state->frames.erase(it);
+        bool others = t_state->limbo.count(s) != 0;
+        for (auto &kv : t_state->frames) others = others || kv.second.stream == s;
+        auto pq = t_state->pending.find(s);
+        others = others || (pq != t_state->pending.end() && pq->second.jobs.count);
+        if (held && !others) released.add(s);  // (nothing else of the stream can still read what was held for it)
+      } else if (frame_reads_touch(d, r)) {
+        if (d.overWait) {
+          hold = hold_tag(d.stream);
+          d.held = true;
+          ++it;
+        } else {
+          released.add(d.stream);
+          materialize_frame(it);
+          it = t_state->frames.begin();
+        }
+      } else {
+        ++it;
+      }
+    }
     forget_run_expansions(r);
     // a journal dies with its index vector or with a column its filters read — unless a queue the
     // host has already waited for still refers to it (then the block is held below, contents intact)
@@ -178,6 +207,8 @@ void hook_on_access(int device, const void *ptr, size_t bytes) {
         launch_queue(kv.first, kv.second);
       }
     }
+    // a scratch frame defined as a constant chain: the copy reads it, or writes into it or into what it is made from
+    if (!t_state->frames.empty()) materialize_frames(&r, /*readsToo=*/true);
     forget_run_expansions(r);  // (a copy INTO a run-length column: later calls decode it again)
     materialize_fills(&r, &t_syncAfterUnlock);  // (the copy may run on another stream: wait for the fill)
     materialize_limbo(&r, &released);
@@ -229,6 +260,7 @@ void hook_on_stream_destroy(int device, void *streamPtr) {
         }
       }
       t_state->pending.erase(stream);
+      erase_if(t_state->frames, [&](auto &kv) { return kv.second.stream == stream; });
       t_state->expansions.erase(stream);
       scan_ahead_stream_gone(device, stream);  // (the stream's hint, and the regions of a scan launched from it)
       auto lim = t_state->limbo.find(stream);

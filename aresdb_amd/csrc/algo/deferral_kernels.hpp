@@ -129,6 +129,7 @@ __global__ __launch_bounds__(kBlock) void transform_fast_kernel(FastOperands f, 
     uint32_t rows[kTQ][4], vals[kTQ][4], okb[kTQ];
     load_rows<kTQ>(f.idx, f.pad, tq + threadIdx.x, n, rows);
     load_values<kTQ>(f, f.pad, tq + threadIdx.x, n, rows, vals, okb);
+    if (f.chain.n) apply_chain<kTQ>(f, vals);  // (a constant chain: launch-uniform, the chain-free path is as it was)
     store_tile<kTQ, true>(f, s, f.pad, tq + threadIdx.x, n, rows, vals, okb);
   }
 }
@@ -147,6 +148,7 @@ __global__ __launch_bounds__(kBlock, 3) void transform_multi_kernel(MultiJobs jo
     for (int j = 0; j < jobs.count; j++) {
       uint32_t vals[kTQ][4], okb[kTQ];
       load_values<kTQ>(jobs.f[j], 0, tq + threadIdx.x, n, rows, vals, okb);
+      if (jobs.f[j].chain.n) apply_chain<kTQ>(jobs.f[j], vals);
       store_tile<kTQ, false>(jobs.f[j], jobs.s[j], 0, tq + threadIdx.x, n, rows, vals, okb);
     }
   }

@@ -31,6 +31,24 @@ struct EvalParams {
 struct __attribute__((aligned(4))) U32x4 { uint32_t v[4]; };
 struct __attribute__((aligned(4))) U64x2 { uint64_t v[2]; };
 
+// One step of a constant chain `((col o1 c1) o2 c2) ...` (AresDB's time dimensions: Floor(Plus(ts, off), b), Floor(Mod(ts, 86400),
+// 3600), ...): an inner BinaryTransform node `previous value (functor) constant` whose scratch frame was defined, not written.
+// Integer kinds only, so no conversion on the way ever changes bits: the kinds say which division a divLike step is.
+struct FastStep {
+  uint32_t bbits;   // the constant, in the step's common kind
+  uint8_t functor;  // Plus, Minus, Multiply, Divide, Mod or Floor
+  uint8_t I, rk;    // common input kind and result kind: K_I32 or K_U32
+  uint8_t sk;       // the kind the step's scratch frame stored the result as
+  uint8_t bkind;    // the constant's own kind
+  uint8_t divLike;  // Divide / Mod / Floor: the multiply-high division, on magnitudes when I is K_I32
+  uint16_t pad;
+};
+constexpr int kMaxChainSteps = 3;  // steps before the root functor: chains of up to four nodes
+struct FastChain {
+  int n;  // 0: no chain (every expression that is one node)
+  FastStep s[kMaxChainSteps];
+};
+
 // 32-bit column operand + optional constant second operand, as the fast kernels see them
 struct FastOperands {
   const uint32_t *vals;  // column values
@@ -46,8 +64,9 @@ struct FastOperands {
   int streaming;         // non-zero: the column is read once, its loads are non-temporal (set by run_filter_rows)
   int step;              // bytes per stored value: 4, or 2 / 1 (Int16 / Uint16 / Int8 / Uint8 / SmallEnum / BigEnum columns,
                          // widened in registers — sign-extended for akind K_I32 — as query/iterator.hpp:146-165 does)
+  FastChain chain;       // steps applied to the column's value before the functor above (akind stays the COLUMN's stored kind)
 };
-static_assert(sizeof(FastOperands) == 80, "FastOperands is a kernel argument, and the generated kernels' host code reads its fields");
+static_assert(sizeof(FastOperands) == 120, "FastOperands is a kernel argument, and the generated kernels' host code reads its fields");
 // bytes of `rows` values of the operand's column
 __host__ __device__ inline uint64_t fast_value_bytes(const FastOperands &f, uint64_t rows) { return static_cast<uint64_t>(f.step ? f.step : 4) * rows; }
 
@@ -86,6 +105,46 @@ __device__ __forceinline__ void fast_divmod(const FastDivisor &fd, uint32_t x, u
   q = __umulhi(x, fd.M);
   r = x - q * fd.d;
   if (r >= fd.d) { q++; r -= fd.d; }
+}
+
+// ---- constant chains -------------------------------------------------------------------------------------------------
+// One step on one value, null handling aside: a null operand travels through every step as "bits 0, null" and the root functor
+// stores bits 0 for it (functor.hpp:337-351), so the steps run on whatever bits there are and the root zeroes once.
+__device__ __forceinline__ uint32_t chain_step_value(const FastStep &st, const FastDivisor &fd, uint32_t x) {
+  if (st.divLike) {
+    uint32_t q, m;
+    if (st.I == K_I32) {  // C++ truncating semantics on magnitudes (eval_fast)
+      const int32_t sx = static_cast<int32_t>(x), sy = static_cast<int32_t>(st.bbits);
+      fast_divmod(fd, sx < 0 ? 0u - x : x, q, m);
+      const uint32_t sq = ((sx < 0) != (sy < 0)) ? 0u - q : q;
+      const uint32_t sm = sx < 0 ? 0u - m : m;
+      return st.functor == Divide ? sq : st.functor == Mod ? sm : x - sm;
+    }
+    fast_divmod(fd, x, q, m);
+    return st.functor == Divide ? q : st.functor == Mod ? m : x - m;
+  }
+  return st.functor == Plus ? x + st.bbits : st.functor == Minus ? x - st.bbits : x * st.bbits;
+}
+__device__ __forceinline__ FastDivisor chain_step_divisor(const FastStep &st) {
+  return make_fast_divisor((st.I == K_I32 && static_cast<int32_t>(st.bbits) < 0) ? 0u - st.bbits : st.bbits);
+}
+// The chain of `f` over the QUADS x 4 loaded values of a tile, in place: one loop per step, the step's shape decided once
+// (a launch-uniform branch).  Callers test f.chain.n first, so the chain-free path runs the code it always ran.
+template <int QUADS>
+__device__ __forceinline__ void apply_chain(const FastOperands &f, uint32_t (&vals)[QUADS][4]) {
+  for (int k = 0; k < f.chain.n; k++) {
+    const FastStep st = f.chain.s[k];
+    const FastDivisor fd = chain_step_divisor(st);
+#pragma unroll
+    for (int q = 0; q < QUADS; q++)
+#pragma unroll
+      for (int j = 0; j < 4; j++) vals[q][j] = chain_step_value(st, fd, vals[q][j]);
+  }
+}
+// ... and over one value (per-group emission, never a hot loop)
+__device__ __forceinline__ uint32_t apply_chain_one(const FastOperands &f, uint32_t x) {
+  for (int k = 0; k < f.chain.n; k++) x = chain_step_value(f.chain.s[k], chain_step_divisor(f.chain.s[k]), x);
+  return x;
 }
 
 // The fast kernels inline this once per element (16-32 copies), so it only covers what the hot
@@ -291,5 +350,36 @@ inline bool fast_operands(const EvalParams &p, FastOperands &f, bool compareOnly
   return true;
 }
 
+// ---- constant chains, host side ---------------------------------------------------------------------------------------
+// Is `previous value (functor) constant` a step a chain may hold?  prevKind: the kind of the value it is applied to (the
+// column's, or the previous step's scratch frame's); storedKind: the kind its own scratch frame (or sink) stores.  Integer kinds
+// on every side — a float, a Bool frame, a null constant or any other functor keeps the node on the kernel it has always had.
+inline bool chain_step_eligible(int prevKind, int functor, int bkind, uint32_t bok, int I, int rk, int storedKind) {
+  auto intKind = [](int k) { return k == K_I32 || k == K_U32; };
+  if (!intKind(prevKind) || !intKind(bkind) || !intKind(I) || !intKind(rk) || !intKind(storedKind) || !bok) return false;
+  return functor == Plus || functor == Minus || functor == Multiply || functor == Divide || functor == Mod || functor == Floor;
+}
+// the root functor of a hot-shape expression as a chain step (its result stored as storedKind)
+inline FastStep chain_step_of(const FastOperands &f, int storedKind) {
+  FastStep st;
+  memset(&st, 0, sizeof(st));
+  st.bbits = host_cvt32(f.bbits, f.bkind, f.I);
+  st.functor = static_cast<uint8_t>(f.functor);
+  st.I = static_cast<uint8_t>(f.I);
+  st.rk = static_cast<uint8_t>(f.rk);
+  st.sk = static_cast<uint8_t>(storedKind);
+  st.bkind = static_cast<uint8_t>(f.bkind);
+  st.divLike = f.divLike ? 1 : 0;
+  return st;
+}
+inline bool fast_chain_equal(const FastChain &a, const FastChain &b) {
+  if (a.n != b.n) return false;
+  for (int k = 0; k < a.n; k++) {
+    const FastStep &x = a.s[k], &y = b.s[k];
+    if (x.bbits != y.bbits || x.functor != y.functor || x.I != y.I || x.rk != y.rk || x.sk != y.sk || x.bkind != y.bkind || x.divLike != y.divLike)
+      return false;
+  }
+  return true;
+}
 
 }  // namespace ares

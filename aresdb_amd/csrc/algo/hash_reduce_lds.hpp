@@ -49,7 +49,7 @@ struct FusedColumn {
   uint32_t step;  // bytes per stored value (FastOperands::step): 4, 2 or 1; 0 reads as 4
 };
 struct FusedExpr {
-  FastOperands f;  // akind / arity / functor / I / rk / constant / divLike (pointers unused)
+  FastOperands f;  // akind / arity / functor / I / rk / constant / divLike / chain (pointers unused)
   int col;
   int outKind;     // kind of the stored dimension value
 };
@@ -77,7 +77,7 @@ struct FusedPlanD {
 inline bool fused_expr_equal(const FusedExpr &a, const FusedExpr &b) {
   return a.col == b.col && a.outKind == b.outKind && a.f.akind == b.f.akind && a.f.arity == b.f.arity && a.f.functor == b.f.functor &&
          a.f.I == b.f.I && a.f.rk == b.f.rk && a.f.bkind == b.f.bkind && a.f.bbits == b.f.bbits && a.f.bok == b.f.bok &&
-         a.f.divLike == b.f.divLike && (a.f.step ? a.f.step : 4) == (b.f.step ? b.f.step : 4);
+         a.f.divLike == b.f.divLike && (a.f.step ? a.f.step : 4) == (b.f.step ? b.f.step : 4) && fast_chain_equal(a.f.chain, b.f.chain);
 }
 inline bool fused_plan_equal(const FusedPlanD &a, const FusedPlanD &b, int nd) {
   if (a.numCols != b.numCols || a.numFilters != b.numFilters || a.measureDtype != b.measureDtype || a.measureWidth != b.measureWidth ||
@@ -95,8 +95,15 @@ inline bool fused_plan_equal(const FusedPlanD &a, const FusedPlanD &b, int nd) {
 }
 inline int fused_dim_width(const FusedPlanD &p, int d) { return p.dimWidth[d] ? p.dimWidth[d] : 4; }
 inline int fused_col_step(const FusedPlanD &p, int c) { return p.cols[c].step ? static_cast<int>(p.cols[c].step) : 4; }
+// a dimension or the measure is a constant chain (FastOperands::chain)
+inline bool fused_plan_chained(const FusedPlanD &p, int nd) {
+  for (int d = 0; d < nd; d++)
+    if (p.dims[d].f.chain.n) return true;
+  return p.measure.col >= 0 && p.measure.f.chain.n != 0;
+}
 inline bool fused_plan_narrow(const FusedPlanD &p, int nd) {
   if (nd > kGenericFusedDims) return true;  // (generated kernels only, like a plan with narrow slots)
+  if (fused_plan_chained(p, nd)) return true;  // (the precompiled generic scan and merge evaluate one node per expression)
   for (int d = 0; d < nd; d++)
     if (fused_dim_width(p, d) != 4) return true;
   for (int c = 0; c < p.numCols; c++)
@@ -109,7 +116,8 @@ inline bool fused_plan_narrow(const FusedPlanD &p, int nd) {
 // (fused_consumers.hip), the fused extension (hash_reduce_lds.hip) and the vector-sourced launcher (hr_rtc.hip).  The struct is
 // memset to zero first; the spec makers (hr_rtc_gen.hpp) and the launches read it field by field.
 inline FusedColumn fused_column_of(const FastOperands &f) { return FusedColumn{f.vals, f.nulls, f.bitOff, static_cast<uint32_t>(f.step ? f.step : 4)}; }
-// the expression without what belongs to one launch (the column lives in its slot, the rows come from the scan)
+// the expression without what belongs to one launch (the column lives in its slot, the rows come from the scan); its chain
+// is shape and stays
 inline FastOperands fused_strip(FastOperands f) {
   f.vals = nullptr;
   f.nulls = nullptr;

@@ -520,7 +520,11 @@ void fill_columns(Args &args, const FusedPlanD &plan) {
     args.nulls[c] = plan.cols[c].nulls;
     args.bitOff[c] = plan.cols[c].bitOff;
   }
-  for (int d = 0; d < kFusedDims; d++) args.k[const_slot_dim(d)] = plan.dims[d].f.bbits;
+  for (int d = 0; d < kFusedDims; d++) {
+    args.k[const_slot_dim(d)] = plan.dims[d].f.bbits;
+    for (int k = 0; k < plan.dims[d].f.chain.n && k < kMaxChainSteps; k++) args.k[const_slot_dim_chain(d) + k] = plan.dims[d].f.chain.s[k].bbits;
+  }
+  for (int k = 0; k < plan.measure.f.chain.n && k < kMaxChainSteps; k++) args.k[const_slot_measure_chain() + k] = plan.measure.f.chain.s[k].bbits;
 }
 
 // ARES_HR_PHASES=1 (diagnostics): a kernel family's device buffer of 8 time stamps per workgroup, and its launch count

@@ -35,6 +35,9 @@
 //   * columns of kind int32 / uint32 / float32 (modes 1 and 2);
 //   * dimension / measure: a bare column, or an integer column (Divide | Mod | Floor | Plus | Minus |
 //     Multiply) a valid integer constant, stored without a value conversion;
+//   * ... or a constant CHAIN over an integer column (FastOperands::chain, apply_chain): up to three such steps in front of
+//     that functor, emitted as straight-line code — their + / - / x constants in Args::k, their divisors literals —, the null
+//     row zeroed once, behind the functor;
 //   * filters: a column compared (==, !=, <, <=, >, >=) with a valid constant in the common kind;
 //   * the measure carried as 4 bytes (fused_carry).
 #include <cstdio>
@@ -61,13 +64,33 @@ std::string hex(uint32_t v) {
 
 std::string const_name(int slot) { return "a.k[" + std::to_string(slot) + "]"; }
 
+// `r` = `v` (Divide | Mod | Floor) the literal y in kind I, null handling aside: fast_divmod's rules (d = 0 -> q = r = 0; d = 1 ->
+// q = x, r = 0), the signed forms truncating on magnitudes.  Declares ax, q, m, sq, sm [, xneg]: the caller opens a scope.
+void gen_divlike(std::ostringstream &o, int functor, int I, uint32_t y, const char *v, const char *r) {
+  const bool sgn = I == K_I32;
+  const uint32_t mag = (sgn && static_cast<int32_t>(y) < 0) ? 0u - y : y;
+  const bool yneg = sgn && static_cast<int32_t>(y) < 0;
+  if (sgn) o << "        const bool xneg = (i32)" << v << " < 0; const u32 ax = xneg ? 0u - " << v << " : " << v << ";\n";
+  else o << "        const u32 ax = " << v << ";\n";
+  if (mag == 0) o << "        const u32 q = 0u, m = 0u;\n";
+  else if (mag == 1) o << "        const u32 q = ax, m = 0u;\n";
+  else o << "        const u32 q = ax / " << hex(mag) << ", m = ax % " << hex(mag) << ";\n";
+  if (sgn) {
+    o << "        const u32 sq = (xneg != " << (yneg ? "true" : "false") << ") ? 0u - q : q;\n";
+    o << "        const u32 sm = xneg ? 0u - m : m;\n";
+  } else {
+    o << "        const u32 sq = q, sm = m;\n";
+  }
+  o << "        " << r << " = " << (functor == Divide ? "sq" : functor == Mod ? "sm" : std::string(v) + " - sm") << ";\n";
+}
+
 // value expression of one element: writes `r` (result bits) given `v` (stored bits) and `okb` (0/1);
 // `kc` names the run-time constant of the expression.  Returns false when the shape is outside the fast
 // paths of eval_quad.
 // floatArith (the Sort + Reduce scan's measure only): a float column combined with a float constant by Plus / Minus /
 // Multiply (fare * 1.5) — binary32's float branch: one rounding, null -> bits 0.
-bool gen_value(const RtcExpr &f, std::ostringstream &o, const char *v, const char *okb, const char *r, const std::string &kc,
-               bool floatArith = false) {
+bool gen_root_value(const RtcExpr &f, std::ostringstream &o, const char *v, const char *okb, const char *r, const std::string &kc,
+                    bool floatArith) {
   if (!col_kind(f.akind)) return false;
   const bool intKinds = f.akind != K_F32 && f.I != K_F32 && f.akind != K_BOOL;
   if (f.arity == 1) {
@@ -82,25 +105,9 @@ bool gen_value(const RtcExpr &f, std::ostringstream &o, const char *v, const cha
     return true;
   }
   if (f.arity != 2 || !intKinds || !int_kind(f.I) || !int_kind(f.bkind) || !f.bok) return false;
-  const uint32_t y = f.bbits;  // cvt32 between the integer kinds keeps the bits
   if (f.divLike) {  // the divisor is a literal: the compiler turns the division into multiply + shift
-    const bool sgn = f.I == K_I32;
-    const uint32_t mag = (sgn && static_cast<int32_t>(y) < 0) ? 0u - y : y;
-    const bool yneg = sgn && static_cast<int32_t>(y) < 0;
     o << "      {\n";
-    if (sgn) o << "        const bool xneg = (i32)" << v << " < 0; const u32 ax = xneg ? 0u - " << v << " : " << v << ";\n";
-    else o << "        const u32 ax = " << v << ";\n";
-    // fast_divmod: d = 0 -> q = r = 0; d = 1 -> q = x, r = 0
-    if (mag == 0) o << "        const u32 q = 0u, m = 0u;\n";
-    else if (mag == 1) o << "        const u32 q = ax, m = 0u;\n";
-    else o << "        const u32 q = ax / " << hex(mag) << ", m = ax % " << hex(mag) << ";\n";
-    if (sgn) {
-      o << "        const u32 sq = (xneg != " << (yneg ? "true" : "false") << ") ? 0u - q : q;\n";
-      o << "        const u32 sm = xneg ? 0u - m : m;\n";
-    } else {
-      o << "        const u32 sq = q, sm = m;\n";
-    }
-    o << "        " << r << " = " << (f.functor == Divide ? "sq" : f.functor == Mod ? "sm" : std::string(v) + " - sm") << ";\n";
+    gen_divlike(o, f.functor, f.I, f.bbits, v, r);  // cvt32 between the integer kinds keeps the bits
     o << "        if (!" << okb << ") " << r << " = 0u;\n      }\n";
     return true;
   }
@@ -110,6 +117,35 @@ bool gen_value(const RtcExpr &f, std::ostringstream &o, const char *v, const cha
     return true;
   }
   return false;
+}
+
+// ... of an expression with a constant chain in front of its functor (FastOperands::chain): the steps run on the stored bits
+// into `ch`, the functor reads `ch` and zeroes a null row once, at the end (apply_chain + eval_quad of fast_eval.hpp).
+// chainSlot: Args::k slot of the first step's constant (a Plus / Minus / Multiply constant is an argument, a divisor a literal).
+bool gen_value(const RtcExpr &f, std::ostringstream &o, const char *v, const char *okb, const char *r, const std::string &kc, int chainSlot,
+               bool floatArith = false) {
+  if (f.chainN == 0) return gen_root_value(f, o, v, okb, r, kc, floatArith);
+  if (f.chainN < 0 || f.chainN > kMaxChainSteps || chainSlot < 0 || !int_kind(f.akind) || f.arity != 2 || !int_kind(f.I) || !int_kind(f.bkind) ||
+      !f.bok)
+    return false;
+  o << "      {\n      u32 ch = " << v << ";\n";
+  for (int k = 0; k < f.chainN; k++) {
+    const RtcStep &st = f.chain[k];
+    if (!int_kind(st.I)) return false;
+    if (st.divLike) {
+      if (!(st.functor == Divide || st.functor == Mod || st.functor == Floor)) return false;
+      o << "      {\n        u32 t;\n";
+      gen_divlike(o, st.functor, st.I, st.bbits, "ch", "t");
+      o << "        ch = t;\n      }\n";
+    } else if (st.functor == Plus || st.functor == Minus || st.functor == Multiply) {
+      o << "      ch = ch " << (st.functor == Plus ? "+" : st.functor == Minus ? "-" : "*") << " " << const_name(chainSlot + k) << ";\n";
+    } else {
+      return false;
+    }
+  }
+  if (!gen_root_value(f, o, "ch", okb, r, kc, false)) return false;
+  o << "      }\n";
+  return true;
 }
 
 // keep bit of one element for one filter; the constant (converted to the common kind by the host) is `kc`
@@ -885,7 +921,7 @@ std::string generate(const RtcSpec &s) {
       if (e.col != nd) return "";
       o << "#pragma unroll\n  for (int j = 0; j < 4; j++) {\n"
            "    const u32 v = r.v[" << nd << "][j]; const u32 okb = (okc[" << nd << "] >> j) & 1u; u32 x;\n";
-      if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_measure()), sort64)) return "";
+      if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_measure()), const_slot_measure_chain(), sort64)) return "";
       if (avg) {  // avg_measure_float (device_model.hpp) of the expression's value: as measureDtype, then as a float
         const int rk = e.rk;
         if (!(rk == K_F32 || rk == K_I32 || rk == K_U32) || !(s.measureDtype == Float64 || s.measureDtype == Int64)) return "";
@@ -913,7 +949,7 @@ std::string generate(const RtcSpec &s) {
       if (e.col != d || !plain_store(e.rk, e.outKind)) return "";
       o << "#pragma unroll\n  for (int j = 0; j < 4; j++) {\n"
            "    const u32 v = r.v[" << d << "][j]; const u32 okb = (okc[" << d << "] >> j) & 1u; u32 x;\n";
-      if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_dim(d)))) return "";
+      if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_dim(d)), const_slot_dim_chain(d))) return "";
       o << "    h[j] = mix(h[j], x); okbytes[j] |= okb << " << 8 * d << ";\n  }\n";
       prefetch(d);
     }
@@ -933,7 +969,7 @@ std::string generate(const RtcSpec &s) {
         if (e.col != d || !plain_store(e.rk, e.outKind) || (SL.width[d] != 4 && !int_kind(e.rk))) return "";
         o << "#pragma unroll\n  for (int j = 0; j < 4; j++) {\n"
              "    const u32 v = r.v[" << d << "][j]; const u32 okb = (okc[" << d << "] >> j) & 1u; u32 x;\n";
-        if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_dim(d)))) return "";
+        if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_dim(d)), const_slot_dim_chain(d))) return "";
         o << "    xv" << d << "[j] = x" << width_mask(SL.width[d]) << "; xo" << d << "[j] = okb;\n  }\n";
         prefetch(d);
       }
@@ -1314,7 +1350,7 @@ std::string generate_merge(const RtcSpec &s) {
     if (s.nullMask & (1u << c)) o << "    const u32 bit = row + a.bitOff[" << c << "]; const u32 okb = (a.nulls[" << c << "][bit >> 3] >> (bit & 7u)) & 1u;\n";
     else o << "    const u32 okb = 1u;\n";
     o << "    u32 x;\n";
-    if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_dim(d)))) return "";
+    if (!gen_value(e, o, "v", "okb", "x", const_name(const_slot_dim(d)), const_slot_dim_chain(d))) return "";
     o << "    bits[" << d << "] = x; ok[" << d << "] = okb;\n  }\n";
   }
   if (!vectorVW) o << "}\n";
@@ -1676,6 +1712,14 @@ RtcExpr spec_expr(const FusedExpr &e, ExprRole role) {
   if (role == FILTER) return x;
   x.bkind = e.f.bkind; x.divLike = e.f.divLike != 0;
   if (x.divLike) x.bbits = e.f.bbits;
+  // a chain's steps; one this struct cannot hold (or the generator would not answer) declines the whole expression: akind 0
+  x.chainN = e.f.chain.n;
+  if (x.chainN < 0 || x.chainN > kMaxChainSteps) return RtcExpr{};
+  for (int k = 0; k < x.chainN; k++) {
+    const FastStep &st = e.f.chain.s[k];
+    x.chain[k].functor = st.functor; x.chain[k].I = st.I; x.chain[k].divLike = st.divLike != 0;
+    if (st.divLike) x.chain[k].bbits = st.bbits;
+  }
   return x;
 }
 RtcSpec spec_of(RtcKind kind, int nd, int partBits, bool stamps = true) {

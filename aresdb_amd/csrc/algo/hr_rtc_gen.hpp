@@ -13,11 +13,15 @@
 namespace ares {
 namespace hr { struct Widen; }
 
-// slots of Args::k (run-time constants): filter f -> f, dimension d -> kFusedFilters + d, measure -> the last
-constexpr int kNumConsts = kFusedFilters + kFusedDims + 1;
+// slots of Args::k (run-time constants): filter f -> f, dimension d -> kFusedFilters + d, the measure behind them; then the
+// constants of the chain steps (FastOperands::chain) of dimension d and — last — of the measure, kMaxChainSteps each
+constexpr int kNumRootConsts = kFusedFilters + kFusedDims + 1;
+constexpr int kNumConsts = kNumRootConsts + kMaxChainSteps * (kFusedDims + 1);
 constexpr int const_slot_filter(int f) { return f; }
 constexpr int const_slot_dim(int d) { return kFusedFilters + d; }
 constexpr int const_slot_measure() { return kFusedFilters + kFusedDims; }
+constexpr int const_slot_dim_chain(int d) { return kNumRootConsts + kMaxChainSteps * d; }  // step k: + k
+constexpr int const_slot_measure_chain() { return kNumRootConsts + kMaxChainSteps * kFusedDims; }
 
 // The plan-sourced scans (16-byte line records, compact lines, TABLE mode, Sort + Reduce's 64-bit keys), the scans over
 // materialised vectors (HashReduce, Sort + Reduce, HyperLogLog's pre-aggregation) and the two merges.
@@ -29,11 +33,17 @@ enum RtcKind : int32_t {
 const char *rtc_entry_name(int32_t kind);
 
 // What of a FusedExpr is text.  bbits is kept only where it is a literal (divLike: the compiler strength-reduces the
-// division); every other constant travels in Args::k.
+// division); every other constant travels in Args::k.  The same holds for every step of a constant chain.
+struct RtcStep {
+  int32_t functor, I, divLike;
+  uint32_t bbits;
+};
 struct RtcExpr {
   int32_t col, outKind, akind, arity, functor, I, rk, bkind;
   uint32_t bbits, bok;
   int32_t divLike;
+  int32_t chainN;  // steps applied to the column's value before the functor (0: none)
+  RtcStep chain[kMaxChainSteps];
 };
 
 // A kernel's SHAPE: everything its generator reads, and nothing else — the generators see no FusedPlanD, so the text cannot
@@ -54,6 +64,7 @@ struct RtcSpec {
   int32_t vectorVW;                        // bytes of a measure of the vector-sourced scan and merge
   int32_t phases;                          // ARES_HR_PHASES (phases_enabled(), read by the makers)
   int32_t constMeasure;                    // Sort + Reduce: no measure column, the records carry Args::k's measure slot
+  int32_t reserved;                        // (zero: the struct has no padding)
 };
 static_assert(std::has_unique_object_representations<RtcSpec>::value, "compared and hashed as bytes: no padding");
 inline bool operator==(const RtcSpec &a, const RtcSpec &b) { return memcmp(&a, &b, sizeof(a)) == 0; }

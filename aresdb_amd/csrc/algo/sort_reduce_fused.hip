@@ -702,6 +702,7 @@ __device__ __forceinline__ void sr_eval_dim(const FusedPlanD &plan, int d, uint3
   else raw = sgn ? static_cast<uint32_t>(static_cast<int32_t>(reinterpret_cast<const int8_t *>(base)[r])) : base[r];
   const uint32_t rok = col.nulls ? get_bit(col.nulls, r + col.bitOff) : 1u;
   const hr::FusedConst c = hr::fused_const(e.f);
+  if (e.f.chain.n) raw = apply_chain_one(e.f, raw);  // (a constant chain: one value per emitted group)
   const DVal x = eval_fast(e.f, raw, rok, c.y, c.fd);
   *bits = cvt32(x, e.f.rk, e.outKind).bits;
   *ok = x.ok ? 1u : 0u;

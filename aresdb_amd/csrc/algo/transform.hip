@@ -19,11 +19,9 @@
 
 namespace ares {
 
-// Queues one fast-path transform; returns false when deferral is unavailable (the caller launches it).
-static bool defer_transform(int device, hipStream_t stream, const FastOperands &f, const SinkD &s, int n, uint32_t colRows,
-                            std::shared_ptr<StreamBuffer> keep = nullptr) {
-  if (!defer_available()) return false;
-  DeferLock lock(device);
+// Queues one fast-path transform on its stream's queue.  Caller holds the device's DeferLock.
+static void queue_transform(hipStream_t stream, const FastOperands &f, const SinkD &s, int n, uint32_t colRows,
+                            std::shared_ptr<StreamBuffer> keep) {
   // everything pending on OTHER streams of the device is unrelated; only this stream's queue matters
   PendingQueue &q = t_state->pending[stream];
   // what the job reads (the column, the index vector) and writes (the sink's values, its validity bytes)
@@ -52,6 +50,13 @@ static bool defer_transform(int device, hipStream_t stream, const FastOperands &
   q.reads.insert(q.reads.end(), reads, reads + nr);
   q.writes.insert(q.writes.end(), writes, writes + nw);
   if (keep) q.keep.push_back(std::move(keep));
+}
+// ... taking the lock; returns false when deferral is unavailable (the caller launches it).
+static bool defer_transform(int device, hipStream_t stream, const FastOperands &f, const SinkD &s, int n, uint32_t colRows,
+                            std::shared_ptr<StreamBuffer> keep = nullptr) {
+  if (!defer_available()) return false;
+  DeferLock lock(device);
+  queue_transform(stream, f, s, n, colRows, std::move(keep));
   return true;
 }
 
@@ -223,6 +228,102 @@ static bool foreign_gather_enabled() {
   return on.get();
 }
 
+// ---- constant chains: scratch frames defined, not written (deferral.hpp: FrameDef) ---------------------------------------------
+namespace {
+ByteRange scratch_operand_range(const OperandD &op, int n) { return range_of(op.base, static_cast<size_t>(op.nullsOff) + static_cast<size_t>(n)); }
+// caller holds the device's DeferLock: a kernel of the calling entry point is about to write the sink's rows
+void settle_frames_for_sink(const SinkD &s, int n) {
+  if (t_state->frames.empty()) return;
+  settle_frames_for_write(range_of(s.values, static_cast<size_t>(s.width) * n));
+  if (s.nulls) settle_frames_for_write(range_of(s.nulls, static_cast<size_t>(n)));
+}
+// the index vector a job over `indexVector` reads: none where rows are positions (caller holds the device's DeferLock)
+const uint32_t *rows_of(const uint32_t *indexVector, int n) { return (indexVector && !lazy_iota(indexVector, n)) ? indexVector : nullptr; }
+}  // namespace
+
+// A transform call while chains are on.  true: the call is done without a kernel —
+//   * its first operand is a DEFINED frame (same pointer, validity offset, kind, rows, index vector and stream), its second an
+//     eligible constant and the chain has room: it is composed — into a 4-byte integer scratch sink a new definition, into a
+//     dimension or measure sink a queued job that reads the frame's COLUMN;
+//   * or it is itself `column (op) constant` of the hot shape into a 4-byte integer scratch frame: the frame is defined.
+// false: the call runs as ever; the frames it is handed were written first, those it overwrites retired (I1, I2).
+static bool chain_transform(int device, hipStream_t stream, const EvalParams &p, const SinkD &s, const uint32_t *indexVector, int n,
+                            const uint32_t *baseCounts, const std::shared_ptr<StreamBuffer> &decoded) {
+  DeferLock lock(device);
+  const bool intFrame = s.type == SINK_SCRATCH && s.width == 4 && (s.dtype == Int32 || s.dtype == Uint32);
+  const bool queuedSink = (s.type == SINK_DIM || s.type == SINK_MEASURE) && fast_sink(s) && !(s.type == SINK_MEASURE && s.agg == AGGR_AVG_FLOAT);
+  if (p.arity == 2 && p.a.type == OP_SCRATCH && p.b.type == OP_CONST && !baseCounts && (intFrame || queuedSink)) {
+    auto it = t_state->frames.find(const_cast<uint8_t *>(p.a.base));
+    if (it != t_state->frames.end()) {
+      const FrameDef d = it->second;
+      const int frameKind = fused_kind_of(d.s.dtype);
+      const bool same = d.stream == stream && d.n == n && d.idxVec == indexVector && d.s.nulls == p.a.base + p.a.nullsOff && frameKind == p.a.kind;
+      if (same && d.f.chain.n < kMaxChainSteps &&
+          chain_step_eligible(frameKind, p.functor, p.b.kind, p.b.cok, p.I, p.rk, intFrame ? fused_kind_of(s.dtype) : p.rk)) {
+        FastOperands g = d.f;
+        g.chain.s[g.chain.n++] = chain_step_of(d.f, frameKind);
+        g.functor = p.functor;
+        g.I = p.I;
+        g.rk = p.rk;
+        g.bkind = p.b.kind;
+        g.bbits = p.b.cbits;
+        g.bok = p.b.cok;
+        g.divLike = p.functor == Divide || p.functor == Mod || p.functor == Floor;
+        g.idx = rows_of(indexVector, n);
+        g.pad = 0;
+        if (intFrame) {
+          if (s.values == d.s.values) t_state->frames.erase(it);  // the frame is overwritten by its own next node: retired
+          settle_frames_for_sink(s, n);
+          t_state->frames[s.values] = FrameDef{stream, g, s, n, indexVector, d.colRows, d.keep};
+        } else {
+          settle_frames_for_sink(s, n);
+          queue_transform(stream, g, s, n, d.colRows, d.keep);
+        }
+        return true;
+      }
+    }
+  }
+  // not composed: frames the call is handed are written before its kernel reads them, frames it overwrites go
+  if (!t_state->frames.empty()) {
+    if (p.a.type == OP_SCRATCH) {
+      const ByteRange r = scratch_operand_range(p.a, n);
+      materialize_frames(&r, false);
+    }
+    if (p.arity == 2 && p.b.type == OP_SCRATCH) {
+      const ByteRange r = scratch_operand_range(p.b, n);
+      materialize_frames(&r, false);
+    }
+    settle_frames_for_sink(s, n);
+  }
+  FastOperands f;
+  if (!intFrame || baseCounts || !fast_operands(p, f, false) || f.arity != 2 ||
+      !chain_step_eligible(f.akind, f.functor, f.bkind, f.bok, f.I, f.rk, fused_kind_of(s.dtype)))
+    return false;
+  f.idx = rows_of(f.idx, n);
+  // queued transforms that write into the column come first (call order)
+  for (auto &kv : t_state->pending)
+    if (kv.second.jobs.count && column_ranges_touch(kv.second.writes, f, p.a.length)) launch_queue(kv.first, kv.second);
+  t_state->frames[s.values] = FrameDef{stream, f, s, n, indexVector, p.a.length, decoded};
+  return true;
+}
+// ... and a filter call: the frames it is handed are written, those over its index vector too (the vector is about to change)
+static void settle_frames_for_filter(int device, const EvalParams &p, bool isArray, const uint32_t *indexVector, const uint8_t *pred, int n) {
+  if (!chains_enabled()) return;
+  DeferLock lock(device);
+  if (t_state->frames.empty()) return;
+  if (!isArray && p.a.type == OP_SCRATCH) {
+    const ByteRange r = scratch_operand_range(p.a, n);
+    materialize_frames(&r, false);
+  }
+  if (!isArray && p.arity == 2 && p.b.type == OP_SCRATCH) {
+    const ByteRange r = scratch_operand_range(p.b, n);
+    materialize_frames(&r, false);
+  }
+  materialize_frames_of_index(indexVector);
+  if (indexVector) settle_frames_for_write(range_of(indexVector, 4ull * static_cast<size_t>(n)));
+  settle_frames_for_write(range_of(pred, static_cast<size_t>(n)));
+}
+
 static int run_transform(const InputVector *ins, int arity, const OutputVector &output, uint32_t *indexVector,
                          int n, uint32_t *baseCounts, uint32_t startCount, int functor, hipStream_t stream, int device) {
   if (n <= 0) {
@@ -240,6 +341,10 @@ static int run_transform(const InputVector *ins, int arity, const OutputVector &
       if (s.nulls) grouped_note_write(device, s.nulls, static_cast<size_t>(n));
     }
     flush_deferred(device);
+    if (chains_enabled()) {
+      DeferLock lock(device);
+      settle_frames_for_sink(s, n);
+    }
     launch_array(a, s, n, stream);
     note_sink(device, s, n);
     return n;
@@ -266,6 +371,8 @@ static int run_transform(const InputVector *ins, int arity, const OutputVector &
   }
   retire_fills_for_write(device, s.values, static_cast<size_t>(s.width) * n);
   if (s.nulls) retire_fills_for_write(device, s.nulls, static_cast<size_t>(n));
+  // constant chains: an inner node of the hot shape is defined, the node over a defined frame composed (no flush, no kernel)
+  if (chains_enabled() && chain_transform(device, stream, p, s, indexVector, n, baseCounts, decoded)) return n;
   FastOperands f;
   bool fast = fast_sink(s) && fast_operands(p, f, false);
   if (fast && s.type == SINK_DIM && s.width < 4 && !(f.rk == K_I32 || f.rk == K_U32)) fast = false;  // float -> narrow integer: generic kernel
@@ -672,6 +779,7 @@ static int run_filter(const InputVector *ins, int arity, uint32_t *indexVector, 
     decoded = decode_run_length_operand(device, stream, p.a, indexVector, baseCounts, startCount);
   }
   p.needRow = 1;
+  settle_frames_for_filter(device, p, isArray, indexVector, pred, n);
   bool virtualIdx = false;
   const bool rowSpace = prepare_filter(device, stream, p, indexVector, pred, n, numForeignTables, baseCounts, &virtualIdx);
   FastOperands f;

@@ -70,7 +70,20 @@ void AresMemSetFlushHook(void (*hook)(int device));      /* exported by libmem.s
  * The same bookkeeping lets a fast filter return its survivor count without compacting the index
  * vector yet (the predicate vector is written): the compaction runs as soon as anything reads the
  * vector — a second filter, transforms that are launched after all, a copy, any other entry point —
- * and never when HashReduce re-derives the survivors itself.  ARES_LAZY_COMPACT=0 compacts at once. */
+ * and never when HashReduce re-derives the survivors itself.  ARES_LAZY_COMPACT=0 compacts at once.
+ *
+ * Constant chains.  An INNER node of the hot shape — BinaryTransform(column, constant) or BinaryTransform(such a scratch
+ * frame, constant) over integer kinds with Plus, Minus, Multiply, Divide, Mod or Floor, into a 4-byte Int32 / Uint32 scratch
+ * frame, no base counts — is recorded, not launched, and flushes nothing (the time dimensions of query/time_bucketizer.go:
+ * Floor(Plus(ts, off), b), Floor(Mod(ts, 86400), 3600), ... up to four nodes).  The root node over such a frame becomes an
+ * ordinary pending transform that reads the COLUMN, so the batch's queue — and the HashReduce / Sort + Reduce that consumes it —
+ * stays intact.  Flush points of a defined frame (it is written by one kernel, on its stream, before the reader proceeds):
+ *   - a Transform / Filter call that is handed the frame and does not compose (two-column nodes, unary functors, float
+ *     constants, a fifth node), HashLookup and every other entry point that does not name the bytes it reads;
+ *   - on_access over the frame, over its source column or its index vector; a filter or InitIndexVector over its index vector;
+ *   - on_free of its source column or index vector before the host has waited for the stream (after a wait the block is held).
+ * It is NOT a flush point for a frame: WaitForCudaStream, an unrelated call's flush, the launch of the stream's queue.  A frame
+ * that is overwritten whole, freed, or whose stream is destroyed is dropped unwritten.  ARES_CHAINS=0 switches chains off. */
 typedef struct {
   void (*flush)(int device);
   void (*on_wait)(int device, void *stream);

@@ -260,6 +260,136 @@ def trips_leg(be, dev, rows, batch_rows=1 << 26, steps=3):
     return out
 
 
+def chains_leg(be, dev, rows, batch_rows=1 << 26, steps=3, offset=-28800):
+    """chains: the trips query (two time filters plus status) grouped by city_id and a time dimension that is a constant chain
+    (aresdb_amd/queries.py: time_dimension, from query/time_bucketizer.go) — (a) the hourly bucket in a fixed zone,
+    Floor(Plus(ts, off), 3600); (b) hour of day, Floor(Mod(ts, 86400), 3600); (c) hour of week in a fixed zone, four nodes.
+    Each as SUM(fare) through HashReduce and as COUNT(*) through Sort + Reduce, checked key by key against an exact torch
+    group-by of the same expression.  The inner nodes' scratch frames are defined, not written (ARES_CHAINS=0: written, and
+    the root runs on the generic kernel); kernel times name which."""
+    import dataclasses
+    from aresdb_amd import trips
+    from aresdb_amd.executor import DimensionSpec as Dim
+    batches = trips.trips_shard(rows, batch_rows, seed=11, device=dev)
+    names = [n for n, _ in trips.COLUMNS]
+    vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+    streams = [be.call("CreateCudaStream", 0) for _ in range(2)]
+    bytes_per_row = 4 + 2 + 1 + 4 + 4 / 8
+    null_city = 1023
+
+    def wrap(x):  # int64 -> the int32 it wraps to (an integer literal makes every node signed)
+        return ((x + (1 << 31)) % (1 << 32)) - (1 << 31)
+
+    def floor_to(x, y):  # x - x % y with C's remainder
+        return x - torch.fmod(x, y)
+    values = {"a": lambda t: floor_to(wrap(t + offset), 3600),
+              "b": lambda t: floor_to(torch.fmod(t, 86400), 3600),
+              "c": lambda t: floor_to(torch.fmod(wrap(wrap(t + offset) - 345600), 604800), 3600)}
+    exprs = {"a": ("hour", offset), "b": ("hour of day", 0), "c": ("hour of week", offset)}
+    labels = {"a": "fixed-zone hour", "b": "hour of day", "c": "fixed-zone hour of week"}
+
+    def exact(which):
+        """numpy (key = value u32 * 1024 + city code, sum(fare), count, first row) of the groups"""
+        keys, sums, counts, firsts, base = [], [], [], [], 0
+        for b in batches:
+            ts, city, st, fare = (trips.column_values(b[k]) for k in ("request_at", "city_id", "status", "fare"))
+            ok = {k: b[k].valid() for k in b}
+            keep = (ts >= trips.TIME_RANGE[0]) & (ts < trips.TIME_RANGE[1]) & (st == trips.COMPLETED)
+            for k in ("request_at", "status"):
+                if ok[k] is not None:
+                    keep &= ok[k]
+            v = values[which](ts.to(torch.int64)) & 0xFFFFFFFF
+            c = city.to(torch.int64) & 0xFFFF
+            if ok["city_id"] is not None:
+                c = torch.where(ok["city_id"], c, torch.full_like(c, null_city))
+            mm = fare.to(torch.float64)
+            if ok["fare"] is not None:
+                mm = torch.where(ok["fare"], mm, torch.zeros_like(mm))
+            rows_ = torch.arange(base, base + ts.numel(), dtype=torch.int64, device=dev)[keep]
+            uniq, inv = torch.unique((v * 1024 + c)[keep], return_inverse=True)
+            acc = torch.zeros(uniq.numel(), dtype=torch.float64, device=dev).index_add_(0, inv, mm[keep])
+            cnt = torch.zeros(uniq.numel(), dtype=torch.int64, device=dev).index_add_(0, inv, torch.ones_like(inv))
+            first = torch.full((uniq.numel(),), torch.iinfo(torch.int64).max, dtype=torch.int64, device=dev).scatter_reduce_(0, inv, rows_, reduce="amin")
+            keys.append(uniq.cpu().numpy()); sums.append(acc.cpu().numpy()); counts.append(cnt.cpu().numpy()); firsts.append(first.cpu().numpy())
+            base += ts.numel()
+            del ts, city, st, fare, keep, v, c, mm, rows_, uniq, inv, acc, cnt, first
+        key, inv = np.unique(np.concatenate(keys), return_inverse=True)
+        total, n, first = np.zeros(len(key)), np.zeros(len(key), np.int64), np.full(len(key), np.iinfo(np.int64).max)
+        np.add.at(total, inv, np.concatenate(sums)); np.add.at(n, inv, np.concatenate(counts)); np.minimum.at(first, inv, np.concatenate(firsts))
+        return key, total, n, first
+
+    def compare(fetched, expected, count):
+        dims, valids, meas = fetched
+        key, sums, counts, first = expected
+        if not np.frombuffer(valids[0], np.uint8).all():
+            return {"status": "MISMATCH: a null time bucket survived the time filter"}
+        g_ok = np.frombuffer(valids[1], np.uint8).astype(bool)
+        got_key = np.frombuffer(dims[0], np.uint32).astype(np.int64) * 1024 + np.where(g_ok, np.frombuffer(dims[1], np.uint16).astype(np.int64), null_city)
+        got_val = np.frombuffer(meas, np.uint32).astype(np.float64) if count else np.frombuffer(meas, np.float64)
+        want_key, want_val, merged = key, counts.astype(np.float64), 0
+        if not count:  # HashReduce: groups are 32-bit hashes, rows with equal hashes merge under the first
+            c = key % 1024
+            h = trips.murmur3_32_packed((key // 1024).astype(np.uint32), np.where(c == null_city, 0, c).astype(np.uint32), (c != null_city).astype(np.uint8))
+            order = np.lexsort((first, h))
+            head = np.ones(len(order), bool)
+            head[1:] = h[order][1:] != h[order][:-1]
+            ms = np.zeros(int(head.sum()))
+            np.add.at(ms, np.cumsum(head) - 1, sums[order])
+            want_key, want_val, merged = key[order][head], ms, int(len(key) - head.sum())
+        why = None
+        if len(got_key) != len(want_key):
+            why = f"group count {len(got_key)} != expected {len(want_key)}"
+        else:
+            go, wo = np.argsort(got_key, kind="stable"), np.argsort(want_key, kind="stable")
+            if (got_key[go] != want_key[wo]).any():
+                why = f"{int((got_key[go] != want_key[wo]).sum())} dimension rows differ"
+            elif (got_val[go] != want_val[wo]).any():
+                why = f"{int((got_val[go] != want_val[wo]).sum())} values differ"
+        return {"status": "ok" if why is None else "MISMATCH: " + why, "merged_by_32bit_hash": merged}
+    out = []
+    for which in os.environ.get("CHAINS_QUERIES", "a,b,c").split(","):
+        expected = exact(which)
+        dim = Dim(queries.time_dimension(exprs[which][0], "request_at", exprs[which][1]), abi.Uint32)
+        for count in (False, True):
+            base = trips.trips_plan(count=count)
+            plan = dataclasses.replace(base, dimensions=[dim, base.dimensions[1]])
+            packed = None
+            def run():
+                nonlocal packed
+                q = NativeQuery(be, plan, names, streams=streams)
+                if packed is None:
+                    packed = q.pack_batches(vps)
+                q.run_batches(packed)
+                return q
+            compiles = -1
+            for _ in range(4):  # priming passes: until a pass builds no new kernel (trips_leg)
+                run().release()
+                state = be.rtc_wait()
+                if state is None or state["compiles"] == compiles:
+                    break
+                compiles = state["compiles"]
+            passes = []
+            for _ in range(steps):
+                torch.cuda.synchronize(); t0 = time.perf_counter()
+                q = run(); q.release()
+                torch.cuda.synchronize(); passes.append((time.perf_counter() - t0) * 1e3)
+            be.profiler_enable(True)
+            q = run(); torch.cuda.synchronize()
+            kernels = be.profiler_report(); be.profiler_enable(False)
+            rep = compare(q.fetch(), expected, count)
+            groups = q.result_size
+            q.release()
+            out.append({"config": "chains", "dimension": labels[which], "query": "COUNT(*) via Sort+Reduce" if count else "SUM(fare) via HashReduce",
+                        "rows": rows, "batches": len(vps), "batch_rows": batch_rows, "offset": exprs[which][1], "groups": groups,
+                        "key_level_check": rep["status"], "merged_by_32bit_hash": rep.get("merged_by_32bit_hash"),
+                        "ms_per_pass": passes, "ms_per_step": float(np.median(passes)), "rows_per_s": rows / (float(np.median(passes)) * 1e-3),
+                        "algorithmic_bytes_per_row": bytes_per_row, "kernel_ms_per_step": sum(ms for c, ms in kernels.values()),
+                        "kernels": {n: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for n, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
+    for s in streams:
+        be.call("DestroyCudaStream", s, 0)
+    return out
+
+
 def select_leg(be, dev, rows, batch_rows=1 << 26, steps=3, limits=(100, 1000000, -1)):
     """The non-aggregation query over the trips shard (aresdb_amd/trips.py: trips_select_plan — request_at, city_id, fare and a
     UUID key WHERE the two time filters AND status == completed) with limits 100, 1 M and none, through the ordinary sequence
@@ -1091,6 +1221,8 @@ def main():
     if "c4spec" in which: res += c4_spec(be, dev, int(float(os.environ.get("C4_ROWS", "1e9"))), int(float(os.environ.get("C4_KEYS", "5e7"))),
                                          join_columns=os.environ.get("C4_JOIN_COLUMNS", "0") == "1")
     if "trips" in which: res += trips_leg(be, dev, int(float(os.environ.get("TRIPS_ROWS", "1e9"))))
+    if "chains" in which:  # CHAINS_ROWS / CHAINS_BATCH_ROWS; CHAINS_QUERIES: a, b, c (comma separated)
+        res += chains_leg(be, dev, int(float(os.environ.get("CHAINS_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("CHAINS_BATCH_ROWS", str(1 << 26)))))
     if "select" in which:  # SELECT_BATCH_ROWS / SELECT_LIMITS (comma separated, -1 = none): other batch sizes, fewer limits
         res += select_leg(be, dev, int(float(os.environ.get("SELECT_ROWS", str(1 << 28)))), batch_rows=int(float(os.environ.get("SELECT_BATCH_ROWS", str(1 << 26)))),
                           limits=tuple(int(x) for x in os.environ.get("SELECT_LIMITS", "100,1000000,-1").split(",")))

@@ -125,6 +125,12 @@ inline void perturb_expr(std::vector<Perturbation> &out, const std::string &role
   add("bbits", [](FusedExpr &e) { e.f.bbits += 1; });
   add("bok", [](FusedExpr &e) { e.f.bok ^= 1u; });
   add("divLike", [](FusedExpr &e) { e.f.divLike ^= 1; });
+  // the constant chain in front of the functor (FastOperands::chain): its length and its first step
+  add("chain.n", [](FusedExpr &e) { e.f.chain.n = e.f.chain.n ? e.f.chain.n - 1 : 1; });
+  add("chain.functor", [](FusedExpr &e) { e.f.chain.s[0].functor = e.f.chain.s[0].functor == Plus ? Minus : Plus; });
+  add("chain.I", [](FusedExpr &e) { e.f.chain.s[0].I = e.f.chain.s[0].I == K_I32 ? K_U32 : K_I32; });
+  add("chain.bbits", [](FusedExpr &e) { e.f.chain.s[0].bbits += 1; });
+  add("chain.divLike", [](FusedExpr &e) { e.f.chain.s[0].divLike ^= 1; });
 }
 inline std::vector<Perturbation> perturbations(const Shape &base) {
   std::vector<Perturbation> out;
@@ -180,6 +186,8 @@ inline const std::map<std::string, std::string> &over_specified() {
       {"measure.akind/*", "as filter.akind"},
       {"dim.functor/*", "a division-like functor that is neither Divide nor Mod is written as Floor"},
       {"measureDtype/sort64", "a 4-byte measure's dtype is read as Int32, Uint32 or anything else (a float)"},
+      {"dim.chain.I/*", "a step's kind is read where the step divides: Plus / Minus / Multiply wrap alike in both"},
+      {"measure.chain.I/*", "as dim.chain.I"},
       {"measure.rk/*", "read for 4-byte measures, AVG and float arithmetic; an 8-byte sum of a bare column carries the stored bits"},
   };
   return m;
