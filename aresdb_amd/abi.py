@@ -406,12 +406,21 @@ class Backend:
         return slices
 
     def join_column_stats(self):
-        """{batches, declined, rows, probed} of AresJoinColumnsRun since the process started; the caller has waited for its
-        streams."""
+        """{batches, declined, rows, probed} of AresJoinColumnsRun since the process started: probed = 256 or 65536 per direct
+        batch, the rows probed of a probe batch; the caller has waited for its streams."""
         c = (C.c_ulonglong * 4)()
         self._algo.AresJoinColumnStats.argtypes, self._algo.AresJoinColumnStats.restype = [C.POINTER(C.c_ulonglong)], None
         self._algo.AresJoinColumnStats(c)
         return {"batches": int(c[0]), "declined": int(c[1]), "rows": int(c[2]), "probed": int(c[3])}
+
+    def join_column_flavour_stats(self):
+        """{probe, direct, entries} of AresJoinColumnsRun since the process started: batches of either flavour (a batch of
+        zero rows is neither) and the table entries direct batches built, 256 or 65536 each."""
+        c = (C.c_ulonglong * 3)()
+        fn = self._algo.AresJoinColumnFlavourStats  # AttributeError: this library has no such entry point
+        fn.argtypes, fn.restype = [C.POINTER(C.c_ulonglong)], None
+        fn(c)
+        return {"probe": int(c[0]), "direct": int(c[1]), "entries": int(c[2])}
 
     @property
     def has_geo_column(self):

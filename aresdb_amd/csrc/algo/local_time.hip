@@ -21,6 +21,7 @@
 #include "cuckoo_probe.hpp"
 #include "device_model.hpp"
 #include "fast_eval.hpp"
+#include "narrow_key.hpp"
 #include "row_hints.hpp"
 #include "select_scan.hpp"
 
@@ -110,34 +111,10 @@ __global__ __launch_bounds__(kLtBlock) void local_time_table_kernel(LocalTimePla
   const uint32_t v = blockIdx.x * kLtBlock + threadIdx.x;
   if (v >= static_cast<uint32_t>(p.keySpace)) return;
   const FastDivisor bucketDiv = make_fast_divisor(p.index.numBuckets);
-  uint32_t widened = v;
-  if (p.key.kind == K_I32)
-    widened = p.key.step == 2 ? static_cast<uint32_t>(static_cast<int32_t>(static_cast<int16_t>(v)))
-                              : static_cast<uint32_t>(static_cast<int32_t>(static_cast<int8_t>(v)));
-  uint32_t key[4] = {widened, 0, 0, 0};
+  uint32_t key[4] = {widen_stored_key(p.key.kind, p.key.step, v), 0, 0, 0};
   const RecordID rid = cuckoo_probe(p.index, bucketDiv, key);
   const DVal z = load_foreign32(p.zone, rid);
   p.table[v] = z.ok ? z.bits : kNullEntry;
-}
-
-struct __attribute__((packed, aligned(4))) Words4 { uint32_t v[4]; };
-struct __attribute__((packed, aligned(2))) Halves4 { uint16_t v[4]; };
-
-// validity bits first .. first + 3 of a bitmap
-__device__ __forceinline__ uint32_t four_bits(const uint8_t *nulls, uint32_t first) {
-  const uint32_t at = first >> 3, shift = first & 7;
-  uint32_t w = nulls[at];
-  if (shift > 4) w |= static_cast<uint32_t>(nulls[at + 1]) << 8;  // (only then: nothing is read past the bits asked for)
-  return (w >> shift) & 15u;
-}
-
-// bit k of the low 16 bits to bit 4 * k
-__device__ __forceinline__ unsigned long long spread4(unsigned long long x) {
-  x = (x | (x << 24)) & 0x000000ff000000ffull;
-  x = (x | (x << 12)) & 0x000f000f000f000full;
-  x = (x | (x << 6)) & 0x0303030303030303ull;
-  x = (x | (x << 3)) & 0x1111111111111111ull;
-  return x;
 }
 
 __device__ __forceinline__ uint32_t stored_key(const LocalTimeRowsD &p, uint32_t row) {

@@ -332,9 +332,21 @@ void AresSelectJoinStats(unsigned long long *counters);
  * HashLookup takes); 1-4 joined columns of 1-, 2- or 4-byte non-Bool types (a ForeignColumnInput, fields as for UnaryTransform,
  * RecordIDs ignored).  Declined ("not fusable", nothing launched): a Bool or wide joined column, a non-null TimezoneLookup, a
  * mode-0 or run-length key, numColumns outside 1..4, a null or misaligned `out`, ARES_JOIN_COLUMNS=0.
+ * Two flavours, byte-identical on every row that no hint prunes:
+ *   probe — one row and one probe per lane, as above, hints evaluated first.  Every key HashLookup accepts; a narrow key on a
+ *     batch too short for the direct flavour.
+ *   direct — the key column's type is 1 or 2 bytes wide (Int8, Uint8, Int16, Uint16).  A first kernel enumerates all 2^8 or
+ *     2^16 stored key values, widens each as HashLookup does (the column's type decides sign extension, keyBytes what is kept),
+ *     probes once per value and writes, into stream temporaries, 4 bytes of value bits per value and joined column and one byte
+ *     of validity bits per value — at most 65 536 x (4 x 4 + 1) bytes, 1.06 MiB; a second kernel streams over the rows, four
+ *     per lane: keys in, four gathers per column from the table, the values out at the column's width.  No probe per row.
+ *     Hints are NOT evaluated: a row a hint would prune is written as any other row (the host's own filters kill it), so the
+ *     output is the probe flavour's for the same query without hints.  Chosen when the key is narrow and
+ *     batchRows >= 64 x the number of key values (16 384 rows for a 1-byte key, 4 Mi rows for a 2-byte key).
  * res = batchRows.  The call does not wait for the stream; the outputs are reported to libmem.so as written (AresMemNoteWrite).
- * Environment (both obey AresReloadEnv): ARES_JOIN_COLUMNS=0 declines always; ARES_JOIN_COLUMNS_GRID=n (tests) sets the
- * number of workgroups. */
+ * Environment (both obey AresReloadEnv): ARES_JOIN_COLUMNS=0 declines always, =probe / =direct force a flavour where it is
+ * applicable (direct on a 4-byte or wide key still probes), anything else chooses as above; ARES_JOIN_COLUMNS_GRID=n (tests)
+ * sets the number of workgroups. */
 typedef struct {
   InputVector column; /* ForeignColumnInput */
   uint8_t *out;       /* device, 64-byte aligned, AresJoinColumnBytes(batchRows, DataType) bytes */
@@ -351,9 +363,13 @@ typedef struct {
 size_t AresJoinColumnBytes(int rows, enum DataType type); /* 0 for a type the entry point declines */
 CGoCallResHandle AresJoinColumnsRun(const AresJoinColumns *q, int batchRows, VectorPartySlice *outSlices, void *cudaStream,
                                     int device);
-/* {batches run, batches declined, rows, keys probed} since process start; keys probed = rows that passed every evaluated hint
- * and had a valid key, counted on the device: the caller has waited for its streams */
+/* {batches run, batches declined, rows, keys probed} since process start; keys probed = 256 or 65536 for a direct batch, for a
+ * probe batch the rows that passed every evaluated hint and had a valid key, counted on the device: the caller has waited for
+ * its streams */
 void AresJoinColumnStats(unsigned long long *counters);
+/* {probe batches, direct batches, table entries built by direct batches} since process start; a batch of zero rows launches
+ * nothing and is neither */
+void AresJoinColumnFlavourStats(unsigned long long *counters);
 
 /* The geofence verdict of a batch resolved once, in row space: for an AGGREGATION query with a geography_intersects join whose
  * points are a main-table column.  One kernel classifies every row of a batch without base counts (pruning hints, null

@@ -496,9 +496,11 @@ def _trips_join_table(be, dev, batches, nkeys, gen, per_batch=1 << 20):
 def join_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, table_keys=(4000, 50_000_000)):
     """joinagg: the typical joined aggregation — the trips query (two time filters plus status) joined to a dimension table
     (select_join_leg's two tables), grouped by the hour and the joined attribute, with the foreign filter attr < 500 on or off:
-    SUM(fare) through HashReduce and COUNT(*) through Sort + Reduce, each through the per-node join sequence and with
-    AresQuerySetJoinColumns on the same build, results compared key by key.  One JSON row per (keys, foreign filter, query,
-    path): wall ms per step, the per-kernel split and the keys probed in row space."""
+    SUM(fare) through HashReduce and COUNT(*) through Sort + Reduce, each through the per-node join sequence, with
+    AresQuerySetJoinColumns (the flavour AresJoinColumnsRun picks: direct for the 2-byte city_id) and — for city_id — with it under
+    ARES_JOIN_COLUMNS=probe, on the same build, results compared key by key.  The paths alternate pass by pass; ms_per_step is a
+    path's median of at least five.  One JSON row per (keys, foreign filter, query, path): wall ms, the per-kernel split, the
+    keys probed in row space and the batches of either flavour."""
     from aresdb_amd import trips
     from aresdb_amd.executor import Binary, Const
     gen = torch.Generator(device=dev)
@@ -510,39 +512,52 @@ def join_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, table_keys=(4000, 5
         ft, join_column, tb, dcols = _trips_join_table(be, dev, batches, nkeys, gen)
         names = list(batches[0].keys())
         vps = [({k: rc.vp for k, rc in b.items()}, b["fare"].length) for b in batches]
+        key_narrow = join_column == "city_id"
         for with_filter in (True, False):
             for count in (False, True):
-                first = None
-                for on in (False, True):
-                    plan = trips.trips_plan(count=count)
-                    plan.dimensions[1] = DimensionSpec(Col("attr", table=1), abi.Uint32)
-                    plan.foreign_tables = [ft]
-                    plan.foreign_filters = [Binary(abi.LessThan, Col("attr", table=1), Const(500))] if with_filter else []
-                    packed = None
-                    def run():
-                        nonlocal packed
-                        q = NativeQuery(be, plan, names, streams=streams)
-                        q.set_join_columns(on)
-                        if packed is None:
-                            packed = q.pack_batches(vps)
-                        q.run_batches(packed)
-                        return q
+                # per-node: the setter off; default: the setter on, the flavour the library picks (direct for the 2-byte city_id at
+                # these batch sizes); probe: the setter on under ARES_JOIN_COLUMNS=probe (a 4-byte key probes anyway: no such leg)
+                paths = ("per-node", "default", "probe") if key_narrow else ("per-node", "default")
+                plan = trips.trips_plan(count=count)
+                plan.dimensions[1] = DimensionSpec(Col("attr", table=1), abi.Uint32)
+                plan.foreign_tables = [ft]
+                plan.foreign_filters = [Binary(abi.LessThan, Col("attr", table=1), Const(500))] if with_filter else []
+                packed = None
+                def run(path):
+                    nonlocal packed
+                    if path == "probe":
+                        os.environ["ARES_JOIN_COLUMNS"] = "probe"
+                    else:
+                        os.environ.pop("ARES_JOIN_COLUMNS", None)
+                    be.reload_env()
+                    q = NativeQuery(be, plan, names, streams=streams)
+                    q.set_join_columns(path != "per-node")
+                    if packed is None:
+                        packed = q.pack_batches(vps)
+                    q.run_batches(packed)
+                    return q
+                for path in paths:
                     compiles = -1
                     for _ in range(4):  # priming passes: the shape's kernels are compiled in the background
-                        run().release()
+                        run(path).release()
                         state = be.rtc_wait()
                         if state is None or state["compiles"] == compiles:
                             break
                         compiles = state["compiles"]
-                    torch.cuda.synchronize(); t0 = time.perf_counter()
-                    for _ in range(steps):
-                        run().release()
-                    torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / steps
+                passes = {path: [] for path in paths}
+                for _ in range(max(steps, 5)):  # the paths alternate, one pass each; the median per path is reported
+                    for path in paths:
+                        torch.cuda.synchronize(); t0 = time.perf_counter()
+                        run(path).release()
+                        torch.cuda.synchronize(); passes[path].append((time.perf_counter() - t0) * 1e3)
+                first = None
+                for path in paths:
+                    dt = float(np.median(passes[path])) / 1e3
                     be.profiler_enable(True)
-                    stats0 = be.join_column_stats()
-                    q = run(); torch.cuda.synchronize()
+                    stats0, flavours0 = be.join_column_stats(), be.join_column_flavour_stats()
+                    q = run(path); torch.cuda.synchronize()
                     kernels = be.profiler_report(); be.profiler_enable(False)
-                    stats1 = be.join_column_stats()
+                    stats1, flavours1 = be.join_column_stats(), be.join_column_flavour_stats()
                     n, calls = q.result_size, q.calls
                     dims, valids, meas = q.fetch()
                     q.release()
@@ -550,7 +565,7 @@ def join_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, table_keys=(4000, 5
                     keyed = np.stack([dims[0].view(np.uint32), dims[1].view(np.uint32), valids[0].astype(np.uint32), valids[1].astype(np.uint32)], axis=1)
                     result = {tuple(k): v for k, v in zip(keyed.tolist(), values.tolist())}
                     check = "first"
-                    if not on:
+                    if first is None:
                         first = result
                     elif result == first:
                         check = "ok"
@@ -559,12 +574,17 @@ def join_agg_leg(be, dev, rows, batch_rows=1 << 26, steps=3, table_keys=(4000, 5
                         check = "%d (key, value) pairs differ; totals %s" % (differing, "equal" if sum(result.values()) == sum(first.values()) else "DIFFER")
                     kernel_ms = sum(ms for c, ms in kernels.values())
                     out.append({"config": "joinagg", "table_keys": nkeys, "join_column": join_column, "foreign_filter": with_filter,
-                                "query": "COUNT(*) via Sort+Reduce" if count else "SUM(fare) via HashReduce", "join_columns": on, "rows": rows,
+                                "query": "COUNT(*) via Sort+Reduce" if count else "SUM(fare) via HashReduce", "path": path,
+                                "join_columns": path != "per-node", "rows": rows,
                                 "batches": len(vps), "batch_rows": batch_rows, "groups": n, "abi_calls": calls, "check": check,
-                                "keys_probed_in_row_space": stats1["probed"] - stats0["probed"], "ms_per_step": dt * 1e3,
+                                "keys_probed_in_row_space": stats1["probed"] - stats0["probed"],
+                                "direct_batches": flavours1["direct"] - flavours0["direct"], "probe_batches": flavours1["probe"] - flavours0["probe"],
+                                "ms_per_step": dt * 1e3, "ms_per_pass": [round(x, 3) for x in passes[path]],
                                 "ms_per_1B_rows": dt * 1e3 * 1e9 / rows, "kernel_ms_per_step": kernel_ms, "kernel_ms_per_1B_rows": kernel_ms * 1e9 / rows,
                                 "kernels": {k: {"launches": c, "avg_ms": ms / c, "total_ms": ms} for k, (c, ms) in sorted(kernels.items(), key=lambda kv: -kv[1][1])}})
                     print(json.dumps(out[-1]), flush=True)
+                os.environ.pop("ARES_JOIN_COLUMNS", None)
+                be.reload_env()
         tb.free()
         for c in dcols:
             c.free()
